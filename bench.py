@@ -13,6 +13,13 @@ EXACTLY K decode steps on every rank, bracketed by barrier + synchronize;
 `value` is whole-job output tok/s (MAX-elapsed over ranks), p50 TTFT of the
 prefill+migration path rides in `config`.
 
+`--dump-outputs DIR` writes what the last timed step computed (rank 0's
+decode engine: the sampled tokens and a fixed sample of the logits) as
+DIR/<name>.npy; prompts and weights are seeded, so two builds run with the
+same arguments can be compared output for output.  A plain run measures
+only the headline figure; `--full` is where any secondary measurement or
+check belongs.
+
 `--parallel dp` keeps the round-1 per-rank-replica mode (RCCL world for the
 timing collective only); tp/pp shard one engine across ranks.
 
@@ -50,6 +57,15 @@ def parse_args():
                         "tp/pp: all ranks form one sharded engine")
     p.add_argument("--eager", action="store_true",
                    help="disable hipGraph capture")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed "
+                        "step produced on rank 0 (tokens + a fixed sample "
+                        "of the logits) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run every secondary measurement or check; a "
+                        "plain run does only what the headline figure "
+                        "needs (today there are none: TTFT and prefill "
+                        "rate fall out of the setup phase)")
     return p.parse_args()
 
 
@@ -69,7 +85,9 @@ def init_distributed(args, rank: int, world: int, local_rank: int) -> None:
         if torch.cuda.is_available():
             torch.cuda.set_device(local_rank % torch.cuda.device_count())
         return
-    if torch.cuda.is_available():
+    # --device cpu stays on gloo even where GPUs are visible: a CPU run has
+    # no device to pin (and may have more ranks than the node has GPUs)
+    if args.device == "cuda" and torch.cuda.is_available():
         torch.cuda.set_device(local_rank)
         dist.init_process_group(
             "nccl", timeout=timeout,   # = RCCL over xGMI on ROCm
@@ -194,6 +212,11 @@ def main() -> int:
     if distributed:
         import torch.distributed as dist
         dist.barrier()
+    dump_dir = args.dump_outputs if rank == 0 else None
+    if dump_dir:
+        from rbg_amd.engine.pd_bench import dump_outputs, watch_logits
+        timed_seqs = list(eng.scheduler.running)
+        box = watch_logits(eng)
 
     # ---- timed region: exactly K decode steps -----------------------------
     t_start = time.monotonic()
@@ -212,6 +235,8 @@ def main() -> int:
                          else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dump_dir:
+        dump_outputs(dump_dir, timed_seqs, box)
 
     ms_per_step = elapsed / args.steps * 1000.0
     # tp/pp: ONE engine serves the whole job regardless of rank count

@@ -137,6 +137,53 @@ def _prefill_batch(engine: LLMEngine, prompts: List[List[int]],
     return [(s, parked.pop(s.seq_id)) for s in seqs]
 
 
+def watch_logits(engine: LLMEngine) -> Dict[str, torch.Tensor]:
+    """Keep a reference (no copy, no sync) to the logits each step samples
+    from, so the last timed step's can be written out afterwards."""
+    runner = engine.runner
+    box: Dict[str, torch.Tensor] = {}
+    orig = runner.sample_device
+
+    def sample_device(logits, seqs):
+        box["logits"] = logits
+        return orig(logits, seqs)
+    runner.sample_device = sample_device
+    return box
+
+
+DUMP_LOGIT_COLS = 8192
+
+
+def dump_outputs(out_dir: str, seqs: List[Sequence],
+                 box: Dict[str, torch.Tensor]) -> None:
+    """Write what the last decode step produced as ``out_dir/<name>.npy``:
+
+      next_tokens        float64 [B]     the token each sequence received
+      logits_sample      float32 [B, C]  the logits they were sampled from,
+                                         at a fixed seeded set of C columns
+      logits_sample_cols float64 [C]     those vocabulary columns
+
+    The column sample keeps a 128 x 128k-vocab step at 4 MB."""
+    import os
+
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "next_tokens.npy"),
+            np.asarray([s.last_token for s in seqs], dtype=np.float64))
+    if "logits" not in box:         # pp: only the last stage samples
+        return
+    logits = box["logits"].float().cpu().numpy()
+    vocab = logits.shape[-1]
+    cols = np.arange(vocab)
+    if vocab > DUMP_LOGIT_COLS:
+        cols = np.sort(np.random.default_rng(0).choice(
+            vocab, DUMP_LOGIT_COLS, replace=False))
+    np.save(os.path.join(out_dir, "logits_sample.npy"),
+            np.ascontiguousarray(logits[:, cols], dtype=np.float32))
+    np.save(os.path.join(out_dir, "logits_sample_cols.npy"),
+            cols.astype(np.float64))
+
+
 def run_pd(args, rank: int, world: int, device: str) -> Optional[dict]:
     """Returns the result dict on rank 0, None elsewhere.  With world==1
     both engines share the process (and GPU); with world>1 rank 0 hosts
@@ -279,6 +326,10 @@ def run_pd(args, rank: int, world: int, device: str) -> Optional[dict]:
         torch.cuda.synchronize()
     if distributed:
         dist.barrier()
+    dump_dir = getattr(args, "dump_outputs", None) if rank == 0 else None
+    if dump_dir:
+        timed_seqs = list(decode_engine.scheduler.running)
+        box = watch_logits(decode_engine)
 
     # ---- timed region: exactly K decode steps -----------------------------
     t_start = time.monotonic()
@@ -294,6 +345,8 @@ def run_pd(args, rank: int, world: int, device: str) -> Optional[dict]:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if dump_dir:
+        dump_outputs(dump_dir, timed_seqs, box)
     if rank != 0:
         return None
     ttfts.sort()

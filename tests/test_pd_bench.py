@@ -63,6 +63,65 @@ def test_pd_world1_inprocess_cpu():
     assert res["p50_ttft_ms"] > 0
 
 
+def _load_dump(d):
+    import numpy as np
+    return {n: np.load(os.path.join(str(d), n + ".npy"))
+            for n in ("next_tokens", "logits_sample", "logits_sample_cols")}
+
+
+def test_dump_outputs_deterministic_inprocess(tmp_path):
+    """--dump-outputs: the last timed step's tokens + logits land as .npy;
+    same arguments -> identical inputs -> identical dumps; the tokens are
+    the argmax of the dumped logits (greedy sampling)."""
+    import argparse
+
+    import numpy as np
+
+    from rbg_amd.engine.pd_bench import run_pd
+    dumps = []
+    for name in ("a", "b"):
+        args = argparse.Namespace(model="tiny", batch=4, seq_len=64, steps=3,
+                                  warmup=1, eager=True,
+                                  dump_outputs=str(tmp_path / name))
+        res = run_pd(args, rank=0, world=1, device="cpu")
+        assert res["ms_per_step"] > 0
+        dumps.append(_load_dump(tmp_path / name))
+    a, b = dumps
+    assert a["next_tokens"].dtype == np.float64
+    assert a["logits_sample"].dtype == np.float32
+    assert a["next_tokens"].shape == (4,)
+    assert a["logits_sample"].shape == (4, a["logits_sample_cols"].size)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    # tiny model: vocab 512 is below the column-sample threshold, so the
+    # whole row is dumped and the tokens are its argmax
+    assert np.array_equal(a["logits_sample_cols"], np.arange(512))
+    assert np.array_equal(a["logits_sample"].argmax(-1),
+                          a["next_tokens"].astype(np.int64))
+
+
+@pytest.mark.parametrize("parallel", ["pd", "dp"])
+def test_bench_cli_full_and_dump_outputs(tmp_path, parallel):
+    """Plain `bench.py` (no torchrun) accepts --full and --dump-outputs in
+    both code paths; --steps sets the timed step count it reports."""
+    import numpy as np
+    out = subprocess.run(
+        [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] +
+        TINY[:-4] + ["--steps", "3", "--warmup", "1", "--parallel", parallel,
+                     "--full", "--dump-outputs", str(tmp_path / "o")],
+        capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    res = json.loads([ln for ln in out.stdout.splitlines()
+                      if ln.startswith("{") and '"metric"' in ln][-1])
+    assert res["steps"] == 3 and res["ms_per_step"] > 0
+    assert {"metric", "value", "unit", "higher_is_better", "dtype"} <= set(res)
+    d = _load_dump(tmp_path / "o")
+    assert d["next_tokens"].shape == (4,)
+    assert np.isfinite(d["logits_sample"]).all()
+    assert sum(os.path.getsize(os.path.join(str(tmp_path / "o"), f))
+               for f in os.listdir(str(tmp_path / "o"))) <= 64 << 20
+
+
 def test_dp_world2_cpu():
     """The dp fallback mode still works under torchrun (gloo on CPU)."""
     res = _run_bench(2, TINY + ["--parallel", "dp"])
