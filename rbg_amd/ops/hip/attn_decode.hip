@@ -189,8 +189,13 @@ void decode_attn_kernel(
     // flight and the per-iteration vmcnt slack doubles.
     int base = key_begin + wave * 4;
     Bf16x8U k0, v0, k1, v1;
-    load_pair(base, k0, v0);          // row_offset clamps out-of-range
-    load_pair(base + 16, k1, v1);
+    // guarded like the other variants: for an EMPTY split key_begin lies
+    // past the context, so row_offset's clamp-to-key_begin would index the
+    // block table beyond the sequence's pages
+    if (base < key_end) {
+      load_pair(base, k0, v0);        // row_offset clamps out-of-range
+      load_pair(base + 16, k1, v1);
+    }
     for (; base < key_end; base += 32) {
       const bool valid0 = base + group < key_end;
       Bf16x8U a = k0, b = v0;
@@ -377,7 +382,9 @@ __global__ __launch_bounds__(128, DIET ? 4 : 3) void decode_attn_mfma_kernel(
   // staging: lane covers K/V key row = lane>>1 (32 rows), 64-elem chunk
   // = (lane&1)*64; 2 lanes x 128 B = one contiguous page row
   const int srow = lane >> 1, schunk = (lane & 1) * 64;
-  const int pg_last = pg_end - 1;
+  // clamped at 0 so a ctx == 0 row (pg_end == 0) reads btab[0], never
+  // btab[-1]; outside the lambda: the hot loop's address chain is unchanged
+  const int pg_last = max(pg_end - 1, 0);
   auto page_base = [&](int pg, int local) -> size_t {
     // pair page `local` (0/1): clamp to the last real page
     const int p = btab[min(pg + local, pg_last)];
@@ -727,9 +734,10 @@ __global__ __launch_bounds__(128, 4) void decode_attn_pc_kernel(
   const int npairs = max(0, (pg_end - pg_begin + 1) >> 1);
 
   const int* btab = block_tables + (size_t)seq * max_pages;
-  // ctx >= 1 so pg_end >= 1; for empty splits the clamp keeps block-table
-  // reads at the last REAL page (same convention as variant 4)
-  const int pg_last = pg_end - 1;
+  // for empty splits the clamp keeps block-table reads at the last REAL
+  // page (same convention as variant 4); ctx == 0 gives npairs == 0 and
+  // pg_end == 0, so pg_last clamps at 0
+  const int pg_last = max(pg_end - 1, 0);
 
 #define PC_SPIN(fl, want)                                                    \
   while (*(fl) < (want)) __builtin_amdgcn_s_sleep(2)

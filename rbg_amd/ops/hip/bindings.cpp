@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -48,6 +49,31 @@ void check_bf16_contig(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
   TORCH_CHECK(t.scalar_type() == torch::kBFloat16, name, " must be bf16");
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+}
+
+void check_i32_gpu(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.scalar_type() == torch::kInt32, name, " must be int32");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+}
+
+// Paged KV pool views [pages, KVH, page_size, head_dim]: the kernels index
+// them as dense bf16 with a power-of-two page (shift/mask slot math) and
+// 16-byte row vectors, so anything else must raise instead of launching.
+void check_kv_caches(const torch::Tensor& key_cache,
+                     const torch::Tensor& value_cache) {
+  check_bf16_contig(key_cache, "key_cache");
+  check_bf16_contig(value_cache, "value_cache");
+  TORCH_CHECK(key_cache.dim() == 4,
+              "key_cache must be [pages, KVH, page_size, head_dim]");
+  TORCH_CHECK(value_cache.sizes() == key_cache.sizes(),
+              "key_cache/value_cache shape mismatch");
+  const int64_t page_size = key_cache.size(2);
+  TORCH_CHECK(page_size > 0 && (page_size & (page_size - 1)) == 0,
+              "page_size must be a power of two");
+  TORCH_CHECK(key_cache.size(1) > 0, "cache needs at least one KV head");
+  TORCH_CHECK(key_cache.size(3) > 0 && key_cache.size(3) % 8 == 0,
+              "cache head_dim must be a multiple of 8");
 }
 
 torch::Tensor rmsnorm(torch::Tensor x, torch::Tensor weight, double eps) {
@@ -111,11 +137,29 @@ void rope_store_kv(torch::Tensor q, torch::Tensor k, torch::Tensor v,
   TORCH_CHECK(cos_sin.scalar_type() == torch::kFloat32, "cos_sin fp32");
   TORCH_CHECK(positions.scalar_type() == torch::kInt32, "positions int32");
   TORCH_CHECK(slot_mapping.scalar_type() == torch::kInt32, "slots int32");
+  check_kv_caches(key_cache, value_cache);
+  check_i32_gpu(positions, "positions");
+  check_i32_gpu(slot_mapping, "slot_mapping");
+  TORCH_CHECK(cos_sin.is_cuda() && cos_sin.is_contiguous() &&
+              cos_sin.dim() == 2, "cos_sin must be a contiguous 2-D GPU tensor");
   const int tokens = q.size(0);
   const int head_dim = key_cache.size(3);
   const int num_kv_heads = key_cache.size(1);
   const int page_size = key_cache.size(2);
-  const int num_q_heads = (int)(q.numel() / tokens / head_dim);
+  TORCH_CHECK(cos_sin.size(1) == head_dim,
+              "cos_sin row width must equal the cache head_dim");
+  TORCH_CHECK(k.size(0) == tokens && v.size(0) == tokens &&
+              positions.numel() == tokens && slot_mapping.numel() == tokens,
+              "q/k/v/positions/slot_mapping token counts differ");
+  const int64_t q_width = q.numel() / std::max(tokens, 1);
+  const int64_t k_width = k.numel() / std::max(tokens, 1);
+  const int64_t v_width = v.numel() / std::max(tokens, 1);
+  TORCH_CHECK(k_width == (int64_t)num_kv_heads * head_dim && v_width == k_width,
+              "k/v rows must be cache KVH * head_dim wide");
+  TORCH_CHECK(q_width % head_dim == 0,
+              "q row width must be a multiple of the cache head_dim");
+  if (tokens == 0) return;
+  const int num_q_heads = (int)(q_width / head_dim);
   launch_rope_store_kv(q.data_ptr(), k.data_ptr(), v.data_ptr(),
                        key_cache.data_ptr(), value_cache.data_ptr(),
                        cos_sin.data_ptr(), positions.data_ptr(),
@@ -139,15 +183,25 @@ torch::Tensor decode_attention(torch::Tensor q, torch::Tensor key_cache,
   const int num_q_heads = q.size(1);
   const int head_dim = q.size(2);
   TORCH_CHECK(head_dim == 128, "head_dim must be 128");
+  check_kv_caches(key_cache, value_cache);
+  TORCH_CHECK(key_cache.size(3) == 128, "cache head_dim must be 128");
   const int num_kv_heads = key_cache.size(1);
   const int page_size = key_cache.size(2);
-  const int max_pages = block_tables.size(1);
+  TORCH_CHECK(num_q_heads % num_kv_heads == 0,
+              "q heads must be a multiple of the cache KV heads");
   const int qpg = num_q_heads / num_kv_heads;
   TORCH_CHECK(qpg == 1 || qpg == 2 || qpg == 4 || qpg == 8,
               "GQA group must be 1/2/4/8");
-  TORCH_CHECK(block_tables.scalar_type() == torch::kInt32, "tables int32");
-  TORCH_CHECK(context_lens.scalar_type() == torch::kInt32, "lens int32");
+  check_i32_gpu(block_tables, "block_tables");
+  check_i32_gpu(context_lens, "context_lens");
+  TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(0) == num_seqs,
+              "block_tables must be [num_seqs, max_pages]");
+  TORCH_CHECK(context_lens.dim() == 1 && context_lens.size(0) == num_seqs,
+              "context_lens must be [num_seqs]");
+  TORCH_CHECK(num_splits >= 1, "num_splits must be >= 1");
+  const int max_pages = block_tables.size(1);
   auto out = torch::empty({num_seqs, num_q_heads, head_dim}, q.options());
+  if (num_seqs == 0) return out;
   torch::Tensor partial_o, partial_ml;
   void *po = nullptr, *pml = nullptr;
   if (num_splits > 1) {
