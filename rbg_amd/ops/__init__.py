@@ -79,7 +79,7 @@ def linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     # (qkv, 6144) only up to M=64, and never on wide-N (gate_up 28672,
     # where hipBLASLt already streams at ~6 TB/s)
     if (SKINNY_GEMM and _on_gpu(x) and x.dim() == 2 and
-            x.dtype == torch.bfloat16 and x.shape[0] <= 128 and
+            x.dtype == torch.bfloat16 and 1 <= x.shape[0] <= 128 and
             w.shape[0] % 32 == 0 and x.shape[1] % 512 == 0 and
             (w.shape[0] <= 4608 or
              (x.shape[0] <= 64 and w.shape[0] <= 8192))):

@@ -76,13 +76,25 @@ void check_kv_caches(const torch::Tensor& key_cache,
               "cache head_dim must be a multiple of 8");
 }
 
-torch::Tensor rmsnorm(torch::Tensor x, torch::Tensor weight, double eps) {
+// Shared by both norms: the kernels read weight[0 .. hidden) as 16-byte
+// vectors, so a short, strided or non-bf16 weight must raise here.
+int check_norm_args(const torch::Tensor& x, const torch::Tensor& weight) {
   check_bf16_contig(x, "x");
   check_bf16_contig(weight, "weight");
-  const int hidden = x.size(-1);
-  TORCH_CHECK(hidden % 8 == 0, "hidden must be a multiple of 8");
+  TORCH_CHECK(x.dim() >= 1, "x must have a hidden dimension");
+  const int64_t hidden = x.size(-1);
+  TORCH_CHECK(hidden > 0 && hidden % 8 == 0,
+              "hidden must be a positive multiple of 8");
+  TORCH_CHECK(weight.numel() == hidden, "weight must have hidden elements");
+  TORCH_CHECK(weight.device() == x.device(), "x/weight device mismatch");
+  return (int)hidden;
+}
+
+torch::Tensor rmsnorm(torch::Tensor x, torch::Tensor weight, double eps) {
+  const int hidden = check_norm_args(x, weight);
   const int tokens = x.numel() / hidden;
   auto out = torch::empty_like(x);
+  if (tokens == 0) return out;
   launch_rmsnorm(out.data_ptr(), x.data_ptr(), weight.data_ptr(), (float)eps,
                  tokens, hidden, current_stream());
   return out;
@@ -90,11 +102,12 @@ torch::Tensor rmsnorm(torch::Tensor x, torch::Tensor weight, double eps) {
 
 void fused_add_rmsnorm(torch::Tensor x, torch::Tensor residual,
                        torch::Tensor weight, double eps) {
-  check_bf16_contig(x, "x");
+  const int hidden = check_norm_args(x, weight);
   check_bf16_contig(residual, "residual");
-  const int hidden = x.size(-1);
-  TORCH_CHECK(hidden % 8 == 0, "hidden must be a multiple of 8");
+  TORCH_CHECK(residual.sizes() == x.sizes(), "x/residual shape mismatch");
+  TORCH_CHECK(residual.device() == x.device(), "x/residual device mismatch");
   const int tokens = x.numel() / hidden;
+  if (tokens == 0) return;
   launch_fused_add_rmsnorm(x.data_ptr(), residual.data_ptr(),
                            weight.data_ptr(), (float)eps, tokens, hidden,
                            current_stream());
@@ -102,11 +115,17 @@ void fused_add_rmsnorm(torch::Tensor x, torch::Tensor residual,
 
 torch::Tensor silu_mul(torch::Tensor x) {
   check_bf16_contig(x, "x");
+  TORCH_CHECK(x.dim() >= 1, "x must be [..., 2*inter]");
   const int inter2 = x.size(-1);
-  TORCH_CHECK(inter2 % 16 == 0, "2*inter must be a multiple of 16");
+  TORCH_CHECK(inter2 > 0 && inter2 % 16 == 0,
+              "2*inter must be a positive multiple of 16");
   const int inter = inter2 / 2;
   const int tokens = x.numel() / inter2;
-  auto out = torch::empty({x.size(0), inter}, x.options());
+  // the kernel writes numel / (2*inter) rows: keep every leading dimension
+  auto out_sizes = x.sizes().vec();
+  out_sizes.back() = inter;
+  auto out = torch::empty(out_sizes, x.options());
+  if (tokens == 0) return out;
   launch_silu_mul(out.data_ptr(), x.data_ptr(), tokens, inter,
                   current_stream());
   return out;
@@ -291,13 +310,22 @@ torch::Tensor skinny_gemm(torch::Tensor a, torch::Tensor w,
                           int64_t force_splits = 0) {
   check_bf16_contig(a, "a");
   check_bf16_contig(w, "w");
+  TORCH_CHECK(a.dim() == 2 && w.dim() == 2, "a and w must be 2-D");
+  TORCH_CHECK(a.device() == w.device(), "a/w device mismatch");
   const int64_t M = a.size(0), K = a.size(1), N = w.size(0);
   TORCH_CHECK(w.size(1) == K, "K mismatch");
   TORCH_CHECK(skinny_gemm_supported(M, N, K), "unsupported skinny shape");
+  // only SPLITS 1/2/4/8 are instantiated, and each split's k range must be
+  // whole 256-k groups (an even, >= 4 step count): anything else would
+  // launch a kernel whose grid and workspace disagree with its k span
+  TORCH_CHECK(force_splits == 0 || force_splits == 1 || force_splits == 2 ||
+                  force_splits == 4 || force_splits == 8,
+              "force_splits must be 0 (auto), 1, 2, 4 or 8");
+  TORCH_CHECK(force_splits == 0 || K % (force_splits * 256) == 0,
+              "K must be a multiple of force_splits * 256");
   auto c = torch::empty({M, N}, a.options());
-  int splits = force_splits > 0 ? (int)force_splits
-                                : pick_gemm_splits((int)N, (int)K);
-  if (K % (splits * 256) != 0) splits = pick_gemm_splits((int)N, (int)K);
+  const int splits = force_splits > 0 ? (int)force_splits
+                                      : pick_gemm_splits((int)N, (int)K);
   torch::Tensor ws;
   void* wsp = nullptr;
   if (splits > 1) {

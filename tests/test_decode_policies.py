@@ -47,3 +47,65 @@ def test_split_policy_is_batch_deterministic():
     a = [pick_decode_splits(b, 8, 4096, variant=4) for b in range(1, 129)]
     b = [pick_decode_splits(b, 8, 4096, variant=4) for b in range(1, 129)]
     assert a == b
+
+
+class _RecordingHip:
+    """Stands in for the compiled extension: records skinny_gemm calls."""
+
+    def __init__(self):
+        self.calls = []
+
+    def skinny_gemm(self, a, w, force_splits=0):
+        import torch
+        assert a.is_contiguous()
+        self.calls.append((tuple(a.shape), tuple(w.shape)))
+        return torch.zeros(a.shape[0], w.shape[0], dtype=a.dtype)
+
+
+def test_linear_dispatch_table(monkeypatch):
+    """Which shapes ops.linear hands to the custom GEMM: bf16 2-D x with
+    1 <= M <= 128, N % 32 == 0, K % 512 == 0, and N <= 4608 or (M <= 64 and
+    N <= 8192).  Everything else, M = 0 included, is the library's."""
+    import torch
+    import rbg_amd.ops as ops
+
+    stub = _RecordingHip()
+    monkeypatch.setattr(ops, "_hip", stub)
+    monkeypatch.setattr(ops, "_on_gpu", lambda t: True)
+    monkeypatch.setattr(ops, "SKINNY_GEMM", 1)
+
+    def custom(x_shape, N, dtype=torch.bfloat16):
+        x = torch.zeros(x_shape, dtype=dtype)
+        w = torch.zeros(N, x_shape[-1], dtype=dtype)
+        before = len(stub.calls)
+        out = ops.linear(x, w)
+        assert out.shape == tuple(x_shape[:-1]) + (N,) and out.dtype == dtype
+        return len(stub.calls) - before == 1
+
+    assert custom((128, 512), 4096)
+    assert not custom((129, 512), 4096)
+    assert custom((1, 512), 4608)
+    assert custom((128, 512), 4608)
+    assert not custom((128, 512), 4640)
+    assert custom((64, 512), 8192)
+    assert not custom((65, 512), 8192)
+    assert not custom((64, 512), 8224)
+    assert not custom((64, 512), 4112)         # N % 32 != 0
+    assert custom((16, 1024), 64)
+    assert not custom((16, 768), 64)           # K % 512 != 0
+    assert not custom((2, 8, 512), 64)         # 3-D x
+    assert not custom((16, 512), 64, torch.float16)
+    assert not custom((0, 512), 64)            # no rows: F.linear's empty
+    assert custom((16, 512), 64)
+
+    # a column slice reaches the kernel contiguous
+    wide = torch.zeros(16, 1024, dtype=torch.bfloat16)
+    ops.linear(wide[:, 512:], torch.zeros(64, 512, dtype=torch.bfloat16))
+    assert stub.calls[-1] == ((16, 512), (64, 512))
+
+    monkeypatch.setattr(ops, "SKINNY_GEMM", 0)     # RBG_SKINNY_GEMM=0
+    assert not custom((16, 512), 64)
+    monkeypatch.setattr(ops, "SKINNY_GEMM", 1)
+    monkeypatch.setattr(ops, "_on_gpu", lambda t: False)
+    assert not custom((16, 512), 64)
+
