@@ -206,7 +206,10 @@ class LlamaAttention(nn.Module):
             k = ops.rmsnorm(k.contiguous().view(-1, self.head_dim),
                             self.k_norm,
                             self.cfg.rms_eps).view(T, self.kv_out)
-            v = v.contiguous()
+            # k is now compact, so v must be too (the kernels take ONE k/v
+            # token stride).  Not .contiguous(): for T == 1 it returns the
+            # slice itself, still carrying the fused buffer's row stride
+            v = v.clone(memory_format=torch.contiguous_format)
         key_cache = kv.key_cache(self.layer_idx)
         value_cache = kv.value_cache(self.layer_idx)
         # fused RoPE + paged KV write (q,k rotated in place)
