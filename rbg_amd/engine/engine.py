@@ -10,7 +10,9 @@ scrapes (tok/s, TTFT, pool occupancy).
 from __future__ import annotations
 
 import collections
+import dataclasses
 import logging
+import random
 import time
 from dataclasses import dataclass, field
 from typing import Deque, Dict, List, Optional
@@ -67,11 +69,21 @@ class LLMEngine:
         self.runner = ModelRunner(cfg, tp, pp)
         self.scheduler = Scheduler(cfg, self.runner.cache)
         self.stats = EngineStats()
+        # seeds for requests that bring none: one engine-owned stream, so a
+        # whole run is reproducible and TP ranks (which apply the same
+        # submit ops in the same order) assign identical seeds
+        self._seed_rng = random.Random(cfg.seed)
 
     # ------------------------------------------------------------------
 
     def add_request(self, prompt_tokens: List[int],
                     sampling: Optional[SamplingParams] = None) -> Sequence:
+        sampling = sampling or SamplingParams()
+        sampling.validate()
+        if sampling.seed is None:
+            # a copy: generate() shares one SamplingParams among its prompts
+            sampling = dataclasses.replace(
+                sampling, seed=self._seed_rng.getrandbits(64))
         seq = Sequence(prompt_tokens, sampling)
         limit = min(self.cfg.max_seq_len, self.cfg.model.max_position)
         total = seq.num_prompt_tokens + seq.sampling.max_new_tokens

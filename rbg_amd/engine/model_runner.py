@@ -233,6 +233,14 @@ class ModelRunner:
         hidden = self.model.forward(static["tokens"], batch, self.cache)
         logits = self.model.logits(hidden)
         torch.cuda.synchronize()
+        # Collect dead cycles NOW.  A discarded engine's KV pool is cyclic
+        # garbage (cache <-> prefix cache) whose tensor frees a raw hipMalloc
+        # allocation (kv_cache.py: ipc_alloc_bf16); if the collector happened
+        # to run inside the capture below, that hipFree would invalidate it
+        # (hipErrorStreamCaptureInvalidated).  torch.cuda.graph stopped
+        # collecting on entry by default.
+        import gc
+        gc.collect()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, pool=self._graph_pool):
             hidden = self.model.forward(static["tokens"], batch, self.cache)
@@ -282,8 +290,33 @@ class ModelRunner:
         if all(t == 0.0 for t in temps):
             dev = logits.argmax(dim=-1)
         else:
-            t = torch.tensor([max(tt, 1e-5) for tt in temps],
-                             device=logits.device).unsqueeze(1)
-            probs = torch.softmax(logits / t, dim=-1)
-            dev = torch.multinomial(probs, 1).squeeze(1)
+            # one fused launch for the whole batch; greedy rows in it are
+            # exact argmaxes.  pos is the index the sampled token will take,
+            # so a request's draws depend on (seed, pos) and on nothing else
+            # that shares its batch.
+            import numpy as np
+            from .. import ops as _ops
+            n = len(seqs)
+            sp = [seq.sampling for seq in seqs]
+            # every per-row parameter in ONE staging buffer and one upload
+            # (seven 4-byte words per row; the 8-byte seeds lead so their
+            # int64 view is aligned)
+            buf = np.empty(7 * n, dtype=np.int32)
+            buf[:2 * n].view(np.uint64)[:] = [s.seed or 0 for s in sp]
+            f32 = buf[2 * n:5 * n].view(np.float32)
+            f32[:n] = temps
+            f32[n:2 * n] = [s.top_p for s in sp]
+            f32[2 * n:] = [s.min_p for s in sp]
+            buf[5 * n:6 * n] = [min(s.top_k, 2 ** 31 - 1) for s in sp]
+            buf[6 * n:] = [seq.num_tokens for seq in seqs]
+            w = torch.from_numpy(buf).to(logits.device, non_blocking=True)
+            x = logits if logits.dtype == torch.float32 else logits.float()
+            dev, _ = _ops.sample(
+                x.contiguous(),
+                w[2 * n:3 * n].view(torch.float32),        # temperature
+                w[5 * n:6 * n],                            # top_k
+                w[3 * n:4 * n].view(torch.float32),        # top_p
+                w[4 * n:5 * n].view(torch.float32),        # min_p
+                w[:2 * n].view(torch.int64),               # seed
+                w[6 * n:])                                 # pos
         return dev, dev.tolist()

@@ -28,6 +28,50 @@ class SamplingParams:
     top_p: float = 1.0
     stop_token: Optional[int] = None
     ignore_eos: bool = True        # random-init weights: run to max tokens
+    top_k: int = 0                 # 0 = off
+    min_p: float = 0.0             # 0 = off
+    # 64-bit draw seed; None = LLMEngine.add_request assigns one from the
+    # engine's own generator (docs/FEATURES.md "Seeded sampling")
+    seed: Optional[int] = None
+
+    def validate(self) -> None:
+        """Raise ValueError for parameters outside the sampler's domain."""
+        t, p, mp = self.temperature, self.top_p, self.min_p
+        if not (isinstance(t, (int, float)) and t >= 0 and t < float("inf")):
+            raise ValueError(f"temperature must be finite and >= 0, got {t!r}")
+        if not (isinstance(p, (int, float)) and 0 < p <= 1):
+            raise ValueError(f"top_p must be in (0, 1], got {p!r}")
+        if isinstance(self.top_k, bool) or not isinstance(self.top_k, int) \
+                or not 0 <= self.top_k < 2 ** 31:
+            raise ValueError(f"top_k must be an integer >= 0, got "
+                             f"{self.top_k!r}")
+        if not (isinstance(mp, (int, float)) and 0 <= mp <= 1):
+            raise ValueError(f"min_p must be in [0, 1], got {mp!r}")
+        if self.seed is not None and (
+                isinstance(self.seed, bool) or not isinstance(self.seed, int)
+                or not 0 <= self.seed < 2 ** 64):
+            raise ValueError(f"seed must be an integer in [0, 2^64), got "
+                             f"{self.seed!r}")
+
+    def wire(self) -> dict:
+        """The sampler's parameters as they travel in RPCs and TP ops."""
+        return {"temperature": self.temperature, "top_p": self.top_p,
+                "top_k": self.top_k, "min_p": self.min_p, "seed": self.seed}
+
+    @classmethod
+    def from_wire(cls, max_new_tokens: int, d: Optional[dict] = None,
+                  **legacy) -> "SamplingParams":
+        """Build from a (possibly partial) wire dict; absent fields keep
+        their defaults, so peers that send temperature only still work."""
+        d = dict(d or {})
+        d.update({k: v for k, v in legacy.items() if v is not None})
+        seed = d.get("seed")
+        return cls(max_new_tokens=int(max_new_tokens),
+                   temperature=float(d.get("temperature", 0.0)),
+                   top_p=float(d.get("top_p", 1.0)),
+                   top_k=int(d.get("top_k", 0)),
+                   min_p=float(d.get("min_p", 0.0)),
+                   seed=None if seed is None else int(seed))
 
 
 class Sequence:

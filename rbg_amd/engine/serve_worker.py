@@ -308,8 +308,7 @@ class ServeWorker:
         if kind == "submit":
             seq = self.engine.add_request(
                 list(op["tokens"]),
-                SamplingParams(max_new_tokens=int(op["max_new_tokens"]),
-                               temperature=float(op.get("temperature", 0.0))))
+                SamplingParams.from_wire(op["max_new_tokens"], op))
             self.results[seq.seq_id] = seq
             op["_result"] = seq
         elif kind == "reload":
@@ -322,8 +321,7 @@ class ServeWorker:
             self._release_parked(parked)
         elif kind == "import":
             seq = self._import_alloc(op["tokens"], int(op["num_pages"]),
-                                     int(op["max_new_tokens"]),
-                                     float(op.get("temperature", 0.0)))
+                                     int(op["max_new_tokens"]), op)
             self._import_finish(seq, int(op["first_token"]),
                                 int(op["max_new_tokens"]),
                                 float(op.get("arrival_time", 0.0)),
@@ -445,7 +443,13 @@ class ServeWorker:
     # -- colocated / generic ------------------------------------------------
 
     def _rpc_submit(self, tokens: List[int], max_new_tokens: int = 64,
-                    temperature: float = 0.0) -> int:
+                    temperature: float = 0.0, top_p: float = 1.0,
+                    top_k: int = 0, min_p: float = 0.0,
+                    seed: Optional[int] = None) -> int:
+        sampling = SamplingParams.from_wire(
+            max_new_tokens, temperature=temperature, top_p=top_p,
+            top_k=top_k, min_p=min_p, seed=seed)
+        sampling.validate()
         vocab = self.cfg.model.vocab_size
         if not tokens or min(tokens) < 0 or max(tokens) >= vocab:
             raise ValueError(
@@ -453,16 +457,14 @@ class ServeWorker:
         if self.tp is not None:
             seq = self._tp_submit_op({"kind": "submit", "tokens": tokens,
                                       "max_new_tokens": max_new_tokens,
-                                      "temperature": temperature})
+                                      **sampling.wire()})
             if seq is None:
                 raise RuntimeError("TP lockstep loop did not apply the op")
             return seq.seq_id
         # lock-free: scheduler.waiting is a single-consumer deque (appends
         # are GIL-atomic); taking the engine lock here would convoy behind
         # the never-idle engine loop and serialize admissions
-        seq = self.engine.add_request(
-            tokens, SamplingParams(max_new_tokens=max_new_tokens,
-                                   temperature=temperature))
+        seq = self.engine.add_request(tokens, sampling)
         self.results[seq.seq_id] = seq
         return seq.seq_id
 
@@ -481,8 +483,11 @@ class ServeWorker:
         return [self._rpc_poll(sid) for sid in seq_ids]
 
     def _rpc_generate(self, tokens: List[int], max_new_tokens: int = 64,
-                      temperature: float = 0.0) -> Dict[str, Any]:
-        sid = self._rpc_submit(tokens, max_new_tokens, temperature)
+                      temperature: float = 0.0, top_p: float = 1.0,
+                      top_k: int = 0, min_p: float = 0.0,
+                      seed: Optional[int] = None) -> Dict[str, Any]:
+        sid = self._rpc_submit(tokens, max_new_tokens, temperature, top_p,
+                               top_k, min_p, seed)
         while True:
             res = self._rpc_poll(sid)
             if res["finished"]:
@@ -502,17 +507,23 @@ class ServeWorker:
             cache.free(pages)
 
     def _rpc_prefill(self, tokens: List[int], max_new_tokens: int,
-                     decode_instance: str, temperature: float = 0.0
-                     ) -> Dict[str, Any]:
+                     decode_instance: str, temperature: float = 0.0,
+                     top_p: float = 1.0, top_k: int = 0, min_p: float = 0.0,
+                     seed: Optional[int] = None) -> Dict[str, Any]:
         """Prefill + first token, then migrate KV to the decode peer.
-        Returns the decode-side seq id (or a ticket resolving to it)."""
+        Returns the decode-side seq id (or a ticket resolving to it).
+        The first token is drawn under the request's own parameters, and
+        the seed resolved here travels on, so the decode side continues the
+        same (seed, pos) stream a colocated engine would have used."""
+        first = SamplingParams.from_wire(
+            1, temperature=temperature, top_p=top_p, top_k=top_k,
+            min_p=min_p, seed=seed)
+        first.validate()
         if self.tp is not None:
             seq = self._tp_submit_op({"kind": "submit", "tokens": tokens,
-                                      "max_new_tokens": 1,
-                                      "temperature": 0.0})
+                                      "max_new_tokens": 1, **first.wire()})
         else:
-            seq = self.engine.add_request(
-                tokens, SamplingParams(max_new_tokens=1))
+            seq = self.engine.add_request(tokens, first)
             self.results[seq.seq_id] = seq
         while self._rpc_poll(seq.seq_id)["finished"] is False:
             time.sleep(0.002)
@@ -525,7 +536,7 @@ class ServeWorker:
         first_token = seq.output_tokens[0]
         meta = dict(tokens=tokens, first_token=first_token,
                     num_pages=len(pages), max_new_tokens=max_new_tokens,
-                    temperature=temperature, arrival_time=seq.arrival_time)
+                    arrival_time=seq.arrival_time, **seq.sampling.wire())
         peer_ok = self._peer_possible()
         if self.gcomm is not None:
             client = RpcClient("127.0.0.1",
@@ -596,13 +607,13 @@ class ServeWorker:
     # -- decode role ---------------------------------------------------------
 
     def _import_alloc(self, tokens, num_pages, max_new_tokens,
-                      temperature) -> Sequence:
+                      sampling: Dict[str, Any]) -> Sequence:
         from .kv_cache import BlockTable
         # page allocation is internally locked; everything else here is
         # GIL-atomic against the engine loop
-        seq = Sequence(list(tokens),
-                       SamplingParams(max_new_tokens=max_new_tokens,
-                                      temperature=temperature))
+        params = SamplingParams.from_wire(max_new_tokens, sampling)
+        params.validate()
+        seq = Sequence(list(tokens), params)
         seq.imported_kv = True
         bt = BlockTable(self.engine.runner.cache)
         bt.pages = self.engine.runner.cache.alloc(num_pages)
@@ -643,13 +654,17 @@ class ServeWorker:
                         src_rank: int = -1, src_instance: str = "",
                         temperature: float = 0.0,
                         arrival_time: float = 0.0,
-                        peer_ok: bool = False) -> Dict[str, Any]:
+                        peer_ok: bool = False, top_p: float = 1.0,
+                        top_k: int = 0, min_p: float = 0.0,
+                        seed: Optional[int] = None) -> Dict[str, Any]:
+        sampling = {"temperature": temperature, "top_p": top_p,
+                    "top_k": top_k, "min_p": min_p, "seed": seed}
         if peer_ok and self._peer_possible():
             # xGMI fast path: hand the sender my pool handle + target pages;
             # it pushes directly and then calls import_commit
             from ..parallel import kv_peer
             seq = self._import_alloc(tokens, num_pages, max_new_tokens,
-                                     temperature)
+                                     sampling)
             self._pending_imports[seq.seq_id] = (
                 seq, int(first_token), int(max_new_tokens),
                 float(arrival_time), time.monotonic())
@@ -666,7 +681,7 @@ class ServeWorker:
                     "kind": "import", "ticket": ticket, "tokens": tokens,
                     "first_token": first_token, "num_pages": num_pages,
                     "max_new_tokens": max_new_tokens,
-                    "temperature": temperature,
+                    **sampling,
                     "arrival_time": arrival_time,
                     "src_instance": src_instance})
             return {"ticket": ticket}
@@ -678,7 +693,7 @@ class ServeWorker:
                 "(no comm world and src_rank unset — peer KV mode requires "
                 "GPU engines on both sides)")
         seq = self._import_alloc(tokens, num_pages, max_new_tokens,
-                                 temperature)
+                                 sampling)
 
         def do_recv():
             try:

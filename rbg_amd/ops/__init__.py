@@ -178,3 +178,18 @@ def prefill_attention(q, k, v, cu_seqlens, scale: float,
 
 
 build_cos_sin_table = reference.build_cos_sin_table
+
+
+def sample(logits, temperature, top_k, top_p, min_p, seed, pos):
+    """Seeded sampling, one row per request (docs/FEATURES.md "Seeded
+    sampling").  logits fp32 [n, V]; per-row tensors of length n on the
+    logits' device: fp32 temperature / top_p / min_p, int32 top_k / pos,
+    int64 seed (the 64-bit seed's two's-complement bits).  Returns (tokens
+    int64 [n], num_kept int32 [n]) with no host synchronisation."""
+    if _on_gpu(logits):
+        toks, kept = _require_hip().sample(logits, temperature, top_k, top_p,
+                                           min_p, seed, pos)
+        return toks, kept
+    return reference.sample(logits, temperature, top_k, top_p, min_p, seed,
+                            pos)
+

@@ -34,6 +34,9 @@ void launch_kv_peer_copy(void*, const void*, const void*, const void*, int,
                          int, int, long, long, long, long, hipStream_t);
 void launch_xgmi_allreduce(void*, const void*, void**, void**, int, int,
                            long, hipStream_t);
+void launch_sample(void*, void*, const void*, const void*, const void*,
+                   const void*, const void*, const void*, const void*, int,
+                   int, hipStream_t);
 long xgmi_allreduce_signal_bytes();
 long xgmi_allreduce_error_offset();
 long xgmi_allreduce_counter_offset();
@@ -340,6 +343,46 @@ torch::Tensor skinny_gemm(torch::Tensor a, torch::Tensor w,
   return c;
 }
 
+// ---- fused seeded sampler (ops.sample) -----------------------------------
+// logits fp32 [n, V] contiguous; every per-row parameter is a device tensor
+// of length n, so nothing here reads a value back or synchronises.
+std::vector<torch::Tensor> sample(torch::Tensor logits,
+                                  torch::Tensor temperature,
+                                  torch::Tensor top_k, torch::Tensor top_p,
+                                  torch::Tensor min_p, torch::Tensor seed,
+                                  torch::Tensor pos) {
+  TORCH_CHECK(logits.is_cuda(), "logits must be on GPU");
+  TORCH_CHECK(logits.scalar_type() == torch::kFloat32, "logits must be fp32");
+  TORCH_CHECK(logits.dim() == 2, "logits must be [n, V]");
+  TORCH_CHECK(logits.is_contiguous(), "logits must be contiguous");
+  const int64_t n = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V >= 1, "V must be >= 1");
+  TORCH_CHECK(V <= INT32_MAX && n <= INT32_MAX, "n and V must fit int32");
+  auto check_param = [&](const torch::Tensor& t, torch::ScalarType dt,
+                         const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == logits.device(), name,
+                " must be on the logits' device");
+    TORCH_CHECK(t.scalar_type() == dt, name, " has the wrong dtype");
+    TORCH_CHECK(t.dim() == 1 && t.size(0) == n, name,
+                " must have one entry per row");
+    TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  };
+  check_param(temperature, torch::kFloat32, "temperature");
+  check_param(top_k, torch::kInt32, "top_k");
+  check_param(top_p, torch::kFloat32, "top_p");
+  check_param(min_p, torch::kFloat32, "min_p");
+  check_param(seed, torch::kInt64, "seed");
+  check_param(pos, torch::kInt32, "pos");
+  auto tokens = torch::empty({n}, logits.options().dtype(torch::kInt64));
+  auto kept = torch::empty({n}, logits.options().dtype(torch::kInt32));
+  if (n == 0) return {tokens, kept};
+  launch_sample(tokens.data_ptr(), kept.data_ptr(), logits.data_ptr(),
+                temperature.data_ptr(), top_k.data_ptr(), top_p.data_ptr(),
+                min_p.data_ptr(), seed.data_ptr(), pos.data_ptr(), (int)n,
+                (int)V, current_stream());
+  return {tokens, kept};
+}
+
 // ---- KV-pool IPC export + xGMI peer push (parallel/kv_peer.py) -----------
 // The decode engine's KV pool is allocated with hipMalloc directly (not the
 // caching allocator) so data_ptr() IS the allocation base hipIpcGetMemHandle
@@ -495,6 +538,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mfma_probe32", &mfma_probe32, "32x32x16 MFMA layout probe");
   m.def("skinny_gemm", &skinny_gemm, "decode-shape GEMM (M<=128)",
         py::arg("a"), py::arg("w"), py::arg("force_splits") = 0);
+  m.def("sample", &sample,
+        "seeded top-k/min-p/top-p Gumbel-max sampler -> (tokens, num_kept)");
   // gil_scoped_release on the IPC/copy entry points: mapping or launching
   // against a dying peer can block inside the HIP runtime, and holding the
   // GIL there freezes heartbeats until the controller kills the process

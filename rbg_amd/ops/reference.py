@@ -159,3 +159,113 @@ def prefill_block_info(cu_seqlens: torch.Tensor, qtile: int = 64,
     device = cu_seqlens.device
     return (torch.tensor(infos, dtype=torch.int32, device=device).view(-1, 4),
             torch.tensor(lens, dtype=torch.int32, device=device))
+
+
+# ---------------------------------------------------------------------------
+# seeded sampling (docs/FEATURES.md "Seeded sampling"; hip/sampling.hip)
+# ---------------------------------------------------------------------------
+
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 over numpy uint64 lanes holding 32-bit words.
+    counter: 4 arrays (or ints), key: 2 ints -> 4 uint64 arrays < 2^32."""
+    import numpy as np
+    mask = np.uint64(0xFFFFFFFF)
+    c = [np.asarray(w, dtype=np.uint64) & mask for w in counter]
+    c = list(np.broadcast_arrays(*c))
+    k0, k1 = int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF
+    for _ in range(10):
+        p0 = np.uint64(_PHILOX_M0) * c[0]
+        p1 = np.uint64(_PHILOX_M1) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & mask,
+             (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1), p0 & mask]
+        k0 = (k0 + _PHILOX_W0) & 0xFFFFFFFF
+        k1 = (k1 + _PHILOX_W1) & 0xFFFFFFFF
+    return c
+
+
+def _gumbel_f32(x):
+    """g = -log(-log u), u = ((x >> 8) + 0.5) * 2^-24, in fp32.  The upper
+    half goes through log1p of the exactly representable 1 - u (m + 0.5 is
+    not an fp32 number for m >= 2^23)."""
+    import numpy as np
+    m = (x >> np.uint64(8)).astype(np.int64)
+    f32 = np.float32
+    low = m < (1 << 23)
+    scale = f32(2.0 ** -24)
+    u = (m.astype(f32) + f32(0.5)) * scale
+    v = (((1 << 24) - m).astype(f32) - f32(0.5)) * scale
+    with np.errstate(divide="ignore", invalid="ignore"):
+        w = np.where(low, -np.log(np.where(low, u, f32(0.5))),
+                     -np.log1p(-np.where(low, f32(0.5), v))).astype(f32)
+        return (-np.log(w)).astype(f32)
+
+
+def _sample_row(l, T, k, p, mp, seed, pos):
+    import numpy as np
+    f32 = np.float32
+    V = l.shape[0]
+    l = np.where(np.isnan(l), f32(-np.inf), l).astype(f32)
+    keep = l > f32(-np.inf)
+    if not keep.any():
+        return 0, 0
+    if not T > 0:
+        return int(np.argmax(l)), 1
+    T = f32(T)
+    lmax = l.max()
+    if 0 < k < V:
+        keep &= l >= np.partition(l, V - k)[V - k]
+    if mp > 0:
+        keep &= l >= f32(lmax + f32(T * np.log(f32(mp))))
+    with np.errstate(over="ignore", invalid="ignore"):
+        z = (l / T).astype(f32)
+    if p < 1:
+        # softmax mass as integers in units of 2^-40, like the kernel: the
+        # prefix sums are then exact and independent of summation order
+        idx = np.flatnonzero(keep)
+        with np.errstate(over="ignore", invalid="ignore"):
+            e = np.exp((z[idx] - f32(lmax / T)).astype(f32)).astype(f32)
+        e = np.where(e >= 0, e, f32(0))
+        w = [int(x) for x in np.floor(e.astype(np.float64) * 2.0 ** 40)]
+        order = sorted(range(len(idx)), key=lambda i: -float(l[idx[i]]))
+        total = sum(w)
+        target = max(1, min(total, int(float(f32(p)) * float(total))))
+        acc = 0
+        cut = l[idx[order[-1]]]
+        for i in order:
+            acc += w[i]
+            if acc >= target:
+                cut = l[idx[i]]
+                break
+        keep &= l >= cut
+    idx = np.flatnonzero(keep)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    words = philox4x32_10((idx >> 2, int(pos) & 0xFFFFFFFF, 0, 0),
+                          (seed & 0xFFFFFFFF, seed >> 32))
+    x = np.choose(idx & 3, words)
+    with np.errstate(over="ignore", invalid="ignore"):
+        score = (z[idx] + _gumbel_f32(x)).astype(f32)
+    return int(idx[int(np.argmax(score))]), int(idx.size)
+
+
+def sample(logits: torch.Tensor, temperature: torch.Tensor,
+           top_k: torch.Tensor, top_p: torch.Tensor, min_p: torch.Tensor,
+           seed: torch.Tensor, pos: torch.Tensor
+           ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """CPU twin of hip/sampling.hip: per-row temperature / top-k / min-p /
+    top-p filters, then a Gumbel-max draw over Philox4x32-10 noise keyed by
+    (seed, pos).  fp32 arithmetic in the kernel's order; returns (tokens
+    int64 [n], num_kept int32 [n])."""
+    n = logits.shape[0]
+    rows = logits.detach().float().cpu().numpy()
+    toks = torch.empty(n, dtype=torch.int64)
+    kept = torch.empty(n, dtype=torch.int32)
+    for r in range(n):
+        t, c = _sample_row(rows[r], float(temperature[r]), int(top_k[r]),
+                           float(top_p[r]), float(min_p[r]), int(seed[r]),
+                           int(pos[r]))
+        toks[r], kept[r] = t, c
+    return toks.to(logits.device), kept.to(logits.device)

@@ -19,7 +19,7 @@ import os
 import threading
 import time
 from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
-from typing import Any, Dict, List
+from typing import Any, Dict, List, Optional
 
 from ..runtime.worker import WorkerContext, register_runner
 from .rpc import RpcClient
@@ -234,12 +234,23 @@ class Router:
     # -- request paths -------------------------------------------------------
 
     def generate(self, tokens: List[int], max_new_tokens: int,
-                 temperature: float = 0.0) -> Dict[str, Any]:
-        """Linked-failover continuity: if the dispatched instance dies
+                 temperature: float = 0.0, top_p: float = 1.0,
+                 top_k: int = 0, min_p: float = 0.0,
+                 seed: Optional[int] = None) -> Dict[str, Any]:
+        """Sampling parameters are validated here (ValueError, which the
+        HTTP handler answers with 400) and travel unchanged to the engine.
+
+        Linked-failover continuity: if the dispatched instance dies
         mid-request (InstanceLost from the watcher, or a submit-time
         connection error), the whole request re-dispatches — round-robin
         naturally lands on a surviving replica while the gang recreates
         the dead one."""
+        from ..engine.sequence import SamplingParams
+        sampling = SamplingParams(
+            max_new_tokens=max_new_tokens, temperature=temperature,
+            top_p=top_p, top_k=top_k, min_p=min_p, seed=seed)
+        sampling.validate()
+        sampling = sampling.wire()
         t0 = time.monotonic()
         self._gc_stale()
         window = float(self.ctx.args.get("failover_window_s", 45.0))
@@ -250,9 +261,9 @@ class Router:
             try:
                 if self.mode == "pd":
                     return self._generate_pd(tokens, max_new_tokens,
-                                             temperature, t0)
+                                             sampling, t0)
                 return self._generate_colocated(tokens, max_new_tokens,
-                                                temperature, t0)
+                                                sampling, t0)
             except (InstanceLost, ConnectionError, OSError,
                     RuntimeError) as e:
                 # retryable: instance death, connection refusal during a
@@ -272,24 +283,24 @@ class Router:
                                 attempt, e)
                 time.sleep(0.25)
 
-    def _generate_colocated(self, tokens, max_new_tokens, temperature,
+    def _generate_colocated(self, tokens, max_new_tokens, sampling,
                             t0) -> Dict[str, Any]:
         inst = self._pick_role(self.worker_roles)
         sid = self._client(inst).call("submit", tokens=tokens,
                                       max_new_tokens=max_new_tokens,
-                                      temperature=temperature)
+                                      **sampling)
         res = self._watcher(inst).wait_for(sid, timeout=900.0)
         res["wall_s"] = time.monotonic() - t0
         res["instance"] = inst["name"]
         return res
 
     def _generate_pd(self, tokens: List[int], max_new_tokens: int,
-                     temperature: float, t0: float) -> Dict[str, Any]:
+                     sampling: Dict[str, Any], t0: float) -> Dict[str, Any]:
         prefill = self._pick_role(self.prefill_roles)
         decode = self._pick_role(self.decode_roles)
         pres = self._client(prefill).call(
             "prefill", tokens=tokens, max_new_tokens=max_new_tokens,
-            decode_instance=decode["name"], temperature=temperature)
+            decode_instance=decode["name"], **sampling)
         ttft = time.monotonic() - t0
         dclient = self._client(decode)
         seq_id = pres.get("decode_seq_id")
@@ -324,6 +335,15 @@ class Router:
         return out
 
 
+def _as_int(value: Any, name: str) -> int:
+    """JSON numbers that are whole (3, 3.0) as int; anything else is the
+    client's mistake."""
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or \
+            value != int(value):
+        raise ValueError(f"{name} must be an integer, got {value!r}")
+    return int(value)
+
+
 class _Handler(BaseHTTPRequestHandler):
     router: Router = None   # set by serve()
 
@@ -355,10 +375,15 @@ class _Handler(BaseHTTPRequestHandler):
                 if tokens is None:
                     tokens = simple_tokenize(str(body.get("prompt", "")),
                                              self.router.vocab_size)
+                seed = body.get("seed")
                 res = self.router.generate(
                     tokens,
                     int(body.get("max_tokens", body.get("max_new_tokens", 64))),
-                    float(body.get("temperature", 0.0)))
+                    float(body.get("temperature", 0.0)),
+                    top_p=float(body.get("top_p", 1.0)),
+                    top_k=_as_int(body.get("top_k", 0), "top_k"),
+                    min_p=float(body.get("min_p", 0.0)),
+                    seed=None if seed is None else _as_int(seed, "seed"))
                 if self.path == "/v1/completions":
                     res = {
                         "id": f"cmpl-{int(time.time()*1000)}",
@@ -375,6 +400,9 @@ class _Handler(BaseHTTPRequestHandler):
                 self._reply(200, res)
             else:
                 self._reply(404, {"error": "not found"})
+        except ValueError as e:
+            # malformed JSON or sampling parameters outside their domain
+            self._reply(400, {"error": str(e)})
         except Exception as e:  # noqa: BLE001
             self._reply(500, {"error": repr(e)})
 

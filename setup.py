@@ -27,6 +27,7 @@ HIP_SOURCES = [
     "rope_kv.hip",
     "silu_mul.hip",
     "skinny_gemm.hip",
+    "sampling.hip",
     "kv_peer_copy.hip",
     "allreduce.hip",
     "bindings.cpp",
