@@ -8,6 +8,8 @@ as the implementation.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 
 from . import reference
@@ -27,7 +29,6 @@ def _check_stale() -> None:
     sources (stale-binary guard; the stamp is written by
     __graft_entry__.build())."""
     import hashlib
-    import os
     here = os.path.dirname(os.path.abspath(__file__))
     stamp = os.path.join(here, "_hip_ops.srchash")
     if not os.path.exists(stamp):
@@ -66,7 +67,7 @@ def _on_gpu(t: torch.Tensor) -> bool:
     return t.is_cuda
 
 
-SKINNY_GEMM = int(__import__("os").environ.get("RBG_SKINNY_GEMM", "1"))
+SKINNY_GEMM = int(os.environ.get("RBG_SKINNY_GEMM", "1"))
 
 
 def linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
@@ -141,8 +142,8 @@ def pick_decode_splits(num_seqs: int, num_kv_heads: int,
     return int(min(want, by_ctx, 16))
 
 
-DECODE_VARIANT = int(__import__("os").environ.get("RBG_DECODE_VARIANT", "4"))  # MFMA page-pair decode: 5.6 TB/s vs 4.0 dot2 (B128, within-probe)
-PREFILL_SWZ = int(__import__("os").environ.get("RBG_PREFILL_SWZ", "6"))  # 8-wave + K/V double-buffer (305 TF/s vs 252 @ swz=4, within-probe)
+DECODE_VARIANT = int(os.environ.get("RBG_DECODE_VARIANT", "4"))  # MFMA page-pair decode: 5.6 TB/s vs 4.0 dot2 (B128, within-probe)
+PREFILL_SWZ = int(os.environ.get("RBG_PREFILL_SWZ", "6"))  # 8-wave + K/V double-buffer (305 TF/s vs 252 @ swz=4, within-probe)
 
 
 def decode_attention(q, key_cache, value_cache, block_tables, context_lens,

@@ -1,29 +1,52 @@
 // Paged flash-decode attention (gfx950) — single query token per sequence.
 //
-// HBM-bound: the cost is streaming the sequence's paged K/V once.  Layout
-// and access pattern are designed for that: K/V rows are head_dim=128
-// contiguous bf16 (256 B), read as 16-byte lane vectors by 16-lane groups
-// (4 keys per wave-instruction), GQA handled by computing all q-heads of a
-// kv-head in one pass so K/V bytes are read exactly once.  Split-KV
-// partitions ("flash-decoding") keep >=256 workgroups resident at small
-// batch; partials merge in a combine kernel via the (m, l) log-sum-exp
-// algebra.
+// HBM-bound: the cost is streaming the sequence's paged K/V once, with all
+// q-heads of a kv-head (the GQA group, QPG) computed in one pass so K/V
+// bytes are read exactly once.  Split-KV partitions ("flash-decoding") keep
+// the chip full at small batch; partials merge in decode_combine_kernel via
+// the (m, l) log-sum-exp algebra.
+//
+// Kernels, selected at run time by `variant` (RBG_DECODE_VARIANT):
+//   0-3  decode_attn_kernel: the dot2 family.  K/V rows (128 bf16, 256 B)
+//        are read as 16-byte lane vectors by 16-lane groups, 4 keys per
+//        wave-instruction; any power-of-two page size.
+//   4,5  decode_attn_mfma_kernel: 32-key page-pair tiles on
+//        v_mfma_f32_16x16x32_bf16, one wave per sequence (5 = register
+//        diet).  4 is the default.
+//   6    decode_attn_pc_kernel: the same math split into a producer and a
+//        consumer wave.
+// Variants 4-6 need page_size == 16; with any other page size, and for
+// out-of-range variants, the launcher falls back to variant 1.
 //
 // Capability analog: the decode-side paged attention of the engines the
 // reference orchestrates (SURVEY §2.3 decode engine row).
-#include "common.h"
+#include "attn_mfma.h"
 
 namespace {
 
-constexpr int HEAD_DIM = 128;
-constexpr float NEG_INF = -1e30f;
+// Keys and 16-token pages of one split: the context is cut into 16-key
+// chunks, ceil-divided over the splits (tests/attn_cases._split_range
+// mirrors this rule).  A trailing split may be empty (key_begin >= key_end).
+struct SplitRange { int key_begin, key_end, pg_begin, pg_end; };
+
+DEV_INLINE SplitRange split_range(int ctx, int split, int num_splits) {
+  const int chunk = 16;
+  const int nchunks = (ctx + chunk - 1) / chunk;
+  const int per_split = (nchunks + num_splits - 1) / num_splits;
+  SplitRange r;
+  r.key_begin = split * per_split * chunk;
+  r.key_end = min(ctx, (split + 1) * per_split * chunk);
+  r.pg_begin = r.key_begin >> 4;
+  r.pg_end = (r.key_end + 15) >> 4;
+  return r;
+}
 
 // QPG = q heads per kv head (GQA group). One block = (seq, kv_head, split).
-// 4 waves; each wave covers 4 keys per iteration (16-lane groups, 16 B/lane),
-// 1-ahead K/V prefetch.
-// VARIANT 0: f32 FMA scores (more VGPRs, 3-4 waves/SIMD);
-// VARIANT 1: packed-bf16 v_dot2 scores (96 VGPRs, 5 waves/SIMD for QPG<=4).
-// Runtime-selected (RBG_DECODE_VARIANT) for within-probe A/B.
+// 4 waves; each wave covers 4 keys per iteration (16-lane groups, 16 B/lane).
+// VARIANT 0: f32 FMA scores (more VGPRs, 3-4 waves/SIMD), 1-ahead prefetch;
+// VARIANT 1: packed-bf16 v_dot2 scores (96 VGPRs, 5 waves/SIMD for QPG<=4);
+// VARIANT 2: variant 1 with the page-table address one more iteration ahead;
+// VARIANT 3: variant 1 with a 2-ahead K/V prefetch in named register pairs.
 template <int QPG, int VARIANT>
 __global__ __launch_bounds__(256,
     (VARIANT == 3) ? 4 : ((VARIANT >= 1 && QPG <= 4) ? 5 : 2))
@@ -53,12 +76,8 @@ void decode_attn_kernel(
   const int gl = lane & 15;           // lane within the 16-lane group
   const int dbase = gl * 8;           // this lane's 8 dims
 
-  // split bounds (rounded to 16-key chunks)
-  const int chunk = 16;
-  const int nchunks = (ctx + chunk - 1) / chunk;
-  const int per_split = (nchunks + num_splits - 1) / num_splits;
-  const int key_begin = split * per_split * chunk;
-  const int key_end = min(ctx, (split + 1) * per_split * chunk);
+  const SplitRange sr = split_range(ctx, split, num_splits);
+  const int key_begin = sr.key_begin, key_end = sr.key_end;
 
   // q fragment: VARIANT 1 keeps it packed bf16 (v_dot2 pairs, half the
   // registers); VARIANT 0 pre-converts to f32 with the scale folded in
@@ -277,24 +296,14 @@ void decode_attn_kernel(
 }
 
 
-// V image offset for the decode PV tr-read path (32-key pair image):
-// identical sub-tiling to attn_prefill.hip's v_img_off at ks == 0
-DEV_INLINE int v_img_off(int key, int dim) {
-  const int q = key >> 3, jj = key & 7;
-  return (dim >> 4) * 512 + (jj >> 2) * 256 + q * 64 + (jj & 3) * 16 +
-         (dim & 15);
-}
-
-
 // ---------------------------------------------------------------------------
-// MFMA-tiled decode (VARIANT 4 dispatch): one wave per sequence, 32-key
-// page-pair tiles on v_mfma_f32_16x16x32_bf16 — the prefill kernel's
-// engine applied to decode.  The dot2 kernel (V1) is latency-bound on its
-// serial cross-lane shuffle chain (a group16 reduction round every 4
-// keys, SQ_WAIT_ANY 68%); here one MFMA chain scores 32 keys and the
-// reduction round runs once per PAIR of pages (8x fewer), with PV
-// through the same 32-k fragment + ds_read_b64_tr_b16 V image as
-// attn_prefill.hip.
+// MFMA-tiled decode (variants 4-6): 32-key page-pair tiles on
+// v_mfma_f32_16x16x32_bf16 — the prefill kernel's engine applied to decode.
+// The dot2 kernel (V1) is latency-bound on its serial cross-lane shuffle
+// chain (a group16 reduction round every 4 keys, SQ_WAIT_ANY 68%); here one
+// MFMA chain scores 32 keys and the reduction round runs once per PAIR of
+// pages (8x fewer), with PV through the same 32-k fragment +
+// ds_read_b64_tr_b16 V image as attn_prefill.hip (attn_mfma.h).
 //
 // Layout notes:
 //  * page_size must be 16: a KV page slice [16 tokens][128 d] is 4 KB
@@ -303,348 +312,91 @@ DEV_INLINE int v_img_off(int key, int dim) {
 //    replicate the last head; their outputs are never written).
 //  * S is C-layout: key col = lane&15, q row = 4*(lane>>4)+reg; the two
 //    pages' columns combine lane-locally before ONE group16 max/sum.
-//  * 2-wave workgroups, ~18 KB LDS per wave -> 4 WGs (8 waves) per CU;
-//    MFMA depth inside the wave covers the low waves/SIMD (the same
-//    budget shape as the 8-wave prefill kernel).
-// DIET (variant 5): the round-2 register diet targeting 4 waves/SIMD
-// (docs/ROUND2_DESIGNS.md §1a+1b).  Two changes vs variant 4:
-//  (a) q fragments are RELOADED from global per page pair instead of held
-//      in 16 persistent VGPRs — the rows are the same cache lines every
-//      pair, so after the first touch they come from L1.  Issued BEFORE
-//      the V stage so the compiler's dependency waitcnt for the first S
-//      MFMA is vmcnt(8) (V still in flight), not a pipeline drain.
-//  (b) V stages through 4 of its own registers + 4 of K's (ka0-3 are dead
-//      between DM_WRITE_K and DM_ISSUE_K(pg+2)) — 16 fewer VGPRs.  The
-//      round-67 FULL merge (one 8-set) hit in-loop spills and lost 27%;
-//      this partial merge keeps issue order WAR-safe without aliasing
-//      pressure.  Verified ScratchSize==0 at compile time.
-template <int QPG, int DIET>
-__global__ __launch_bounds__(128, DIET ? 4 : 3) void decode_attn_mfma_kernel(
-    float* __restrict__ partial_o,        // [splits, seqs, QH, D]
-    float* __restrict__ partial_ml,       // [splits, seqs, QH, 2]
-    __hip_bfloat16* __restrict__ out,     // [seqs, QH, D] (splits==1 path)
-    const __hip_bfloat16* __restrict__ q, // [seqs, QH, D]
-    const __hip_bfloat16* __restrict__ key_cache,  // [pages, KVH, 16, D]
-    const __hip_bfloat16* __restrict__ val_cache,
-    const int* __restrict__ block_tables, // [seqs, max_pages]
-    const int* __restrict__ context_lens, // [seqs]
-    const float scale, const int num_kv_heads, const int max_pages,
-    const int num_splits, const int num_seqs, const int q_stride) {
-  typedef __attribute__((ext_vector_type(8))) __bf16 dm_bf8;
-  const int kvh = blockIdx.x;
-  const int wave = threadIdx.x >> 6;
-  const int seq = blockIdx.y * 2 + wave;
-  const int split = blockIdx.z;
-  const int lane = threadIdx.x & 63;
-  const int gl = lane & 15;
-  const int gslice = lane >> 4;
-  const int num_q_heads = num_kv_heads * QPG;
+// The pieces below are shared by the one-wave kernel (4/5) and the
+// producer/consumer kernel (6).
 
-  // per-wave LDS (no cross-wave sharing, no barriers).  K and V SHARE one
-  // buffer: the pair's K panel serves the S MFMAs, then the V image
-  // overwrites it for PV (same-wave DS ops retire in order, so the
-  // write-after-read needs no fence) — halving LDS doubles resident
-  // waves.  V is fully rewritten every pair (tail pages clamp to real
-  // pages and are masked through P=0), so no zero-init is needed.
-  constexpr int KP = 132;                        // k panel pitch (bf16)
-  __shared__ __hip_bfloat16 kv_all[2][32 * KP];  // K panel / V tr image
-  __shared__ __hip_bfloat16 p_lds_all[2][16 * 40];
-  __hip_bfloat16* k_lds = kv_all[wave];
-  __hip_bfloat16* v_img = kv_all[wave];
-  __hip_bfloat16* p_lds = p_lds_all[wave];
-  if (seq >= num_seqs) return;
-  const int ctx = context_lens[seq];
+constexpr int DM_KP = 132;      // K panel pitch (bf16)
+constexpr int DM_PP = 40;       // P tile pitch (bf16)
 
-  const int chunk = 16;
-  const int nchunks = (ctx + chunk - 1) / chunk;
-  const int per_split = (nchunks + num_splits - 1) / num_splits;
-  const int key_begin = split * per_split * chunk;
-  const int key_end = min(ctx, (split + 1) * per_split * chunk);
-  const int pg_begin = key_begin >> 4;
-  const int pg_end = (key_end + 15) >> 4;
-
-  // q fragments: row = head (clamped), 4 k-steps of 32 dims.
-  // DIET: only the row pointer persists; fragments reload per pair (L1).
+// q A-fragments: row = head (clamped), 4 k-steps of 32 dims
+template <int QPG>
+DEV_INLINE void load_q_frags(bf8 (&qa)[4], const __hip_bfloat16* q_seq,
+                             int kvh, int gl, int gslice) {
   const __hip_bfloat16* qrow =
-      q + (size_t)seq * q_stride +
-      (size_t)(kvh * QPG + min(gl, QPG - 1)) * HEAD_DIM;
-  dm_bf8 qa[4];
-  if constexpr (!DIET) {
+      q_seq + (size_t)(kvh * QPG + min(gl, QPG - 1)) * HEAD_DIM;
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      union { uint4 u; dm_bf8 v; } cvt;
-      cvt.u = *reinterpret_cast<const uint4*>(qrow + ks * 32 + gslice * 8);
-      qa[ks] = cvt.v;
-    }
+  for (int ks = 0; ks < 4; ++ks)
+    qa[ks] = load_bf8(qrow + ks * 32 + gslice * 8);
+}
+
+// S = q K^T over the pair's 32 keys (B-frag: key row = gl / gl+16)
+DEV_INLINE void score_pair(f32x4& sA, f32x4& sB, const bf8 (&qa)[4],
+                           const __hip_bfloat16* k_lds, int gl, int gslice) {
+  sA = {0.f, 0.f, 0.f, 0.f};
+  sB = sA;
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    const bf8 kfA = load_bf8(&k_lds[gl * DM_KP + ks * 32 + gslice * 8]);
+    const bf8 kfB = load_bf8(&k_lds[(16 + gl) * DM_KP + ks * 32 + gslice * 8]);
+    sA = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[ks], kfA, sA, 0, 0, 0);
+    sB = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[ks], kfB, sB, 0, 0, 0);
   }
+}
 
-  const int* btab = block_tables + (size_t)seq * max_pages;
-  // staging: lane covers K/V key row = lane>>1 (32 rows), 64-elem chunk
-  // = (lane&1)*64; 2 lanes x 128 B = one contiguous page row
-  const int srow = lane >> 1, schunk = (lane & 1) * 64;
-  // clamped at 0 so a ctx == 0 row (pg_end == 0) reads btab[0], never
-  // btab[-1]; outside the lambda: the hot loop's address chain is unchanged
-  const int pg_last = max(pg_end - 1, 0);
-  auto page_base = [&](int pg, int local) -> size_t {
-    // pair page `local` (0/1): clamp to the last real page
-    const int p = btab[min(pg + local, pg_last)];
-    return (((size_t)p * num_kv_heads + kvh) * 16 + (srow & 15)) * HEAD_DIM +
-           schunk;
-  };
-  const int myloc = srow >> 4;     // which page of the pair this lane stages
-
-  // SCALAR staging registers (docs/cdna_lessons.md §1: local arrays are
-  // demoted to scratch memory, round-tripping every staged page via HBM).
-  // Each lane owns HALF a page row = 64 elements = 8 x 16 B pieces.
-  uint4 ka0, ka1, ka2, ka3, ka4, ka5, ka6, ka7;
-  uint4 va0, va1, va2, va3, va4, va5, va6, va7;
-#define DM_LOAD8(base, r0, r1, r2, r3, r4, r5, r6, r7, off)                 \
-  do {                                                                      \
-    r0 = *reinterpret_cast<const uint4*>(base + off);                       \
-    r1 = *reinterpret_cast<const uint4*>(base + off + 8);                   \
-    r2 = *reinterpret_cast<const uint4*>(base + off + 16);                  \
-    r3 = *reinterpret_cast<const uint4*>(base + off + 24);                  \
-    r4 = *reinterpret_cast<const uint4*>(base + off + 32);                  \
-    r5 = *reinterpret_cast<const uint4*>(base + off + 40);                  \
-    r6 = *reinterpret_cast<const uint4*>(base + off + 48);                  \
-    r7 = *reinterpret_cast<const uint4*>(base + off + 56);                  \
-  } while (0)
-#define DM_ISSUE_K(pg) DM_LOAD8(key_cache, ka0, ka1, ka2, ka3, ka4, ka5,    \
-                                ka6, ka7, page_base(pg, myloc))
-#define DM_ISSUE_V(pg) DM_LOAD8(val_cache, va0, va1, va2, va3, va4, va5,    \
-                                va6, va7, page_base(pg, myloc))
-#define DM_WRITE_K()                                                        \
-  do {                                                                      \
-    *reinterpret_cast<uint4*>(&k_lds[srow * KP + schunk]) = ka0;            \
-    *reinterpret_cast<uint4*>(&k_lds[srow * KP + schunk + 8]) = ka1;        \
-    *reinterpret_cast<uint4*>(&k_lds[srow * KP + schunk + 16]) = ka2;       \
-    *reinterpret_cast<uint4*>(&k_lds[srow * KP + schunk + 24]) = ka3;       \
-    *reinterpret_cast<uint4*>(&k_lds[srow * KP + schunk + 32]) = ka4;       \
-    *reinterpret_cast<uint4*>(&k_lds[srow * KP + schunk + 40]) = ka5;       \
-    *reinterpret_cast<uint4*>(&k_lds[srow * KP + schunk + 48]) = ka6;       \
-    *reinterpret_cast<uint4*>(&k_lds[srow * KP + schunk + 56]) = ka7;       \
-  } while (0)
-#define DM_WRITE_V()                                                        \
-  do {                                                                      \
-    *reinterpret_cast<uint4*>(&v_img[v_img_off(srow, schunk)]) = va0;       \
-    *reinterpret_cast<uint4*>(&v_img[v_img_off(srow, schunk + 8)]) = va1;   \
-    *reinterpret_cast<uint4*>(&v_img[v_img_off(srow, schunk + 16)]) = va2;  \
-    *reinterpret_cast<uint4*>(&v_img[v_img_off(srow, schunk + 24)]) = va3;  \
-    *reinterpret_cast<uint4*>(&v_img[v_img_off(srow, schunk + 32)]) = va4;  \
-    *reinterpret_cast<uint4*>(&v_img[v_img_off(srow, schunk + 40)]) = va5;  \
-    *reinterpret_cast<uint4*>(&v_img[v_img_off(srow, schunk + 48)]) = va6;  \
-    *reinterpret_cast<uint4*>(&v_img[v_img_off(srow, schunk + 56)]) = va7;  \
-  } while (0)
-  // DIET: V stages through vb0-7, declared in the loop with liveness
-  // DISJOINT from the q fragments (qd dies at the last S MFMA; vb issues
-  // right after), so the allocator colors them into the same registers —
-  // V latency hides under the softmax shuffle chain instead of under S.
-#define DM_ISSUE_V_D(pg)                                                    \
-  do {                                                                      \
-    const size_t vb_ = page_base(pg, myloc);                                \
-    vb0 = *reinterpret_cast<const uint4*>(val_cache + vb_);                 \
-    vb1 = *reinterpret_cast<const uint4*>(val_cache + vb_ + 8);             \
-    vb2 = *reinterpret_cast<const uint4*>(val_cache + vb_ + 16);            \
-    vb3 = *reinterpret_cast<const uint4*>(val_cache + vb_ + 24);            \
-    vb4 = *reinterpret_cast<const uint4*>(val_cache + vb_ + 32);            \
-    vb5 = *reinterpret_cast<const uint4*>(val_cache + vb_ + 40);            \
-    vb6 = *reinterpret_cast<const uint4*>(val_cache + vb_ + 48);            \
-    vb7 = *reinterpret_cast<const uint4*>(val_cache + vb_ + 56);            \
-  } while (0)
-#define DM_WRITE_V_D()                                                      \
-  do {                                                                      \
-    *reinterpret_cast<uint4*>(&v_img[v_img_off(srow, schunk)]) = vb0;       \
-    *reinterpret_cast<uint4*>(&v_img[v_img_off(srow, schunk + 8)]) = vb1;   \
-    *reinterpret_cast<uint4*>(&v_img[v_img_off(srow, schunk + 16)]) = vb2;  \
-    *reinterpret_cast<uint4*>(&v_img[v_img_off(srow, schunk + 24)]) = vb3;  \
-    *reinterpret_cast<uint4*>(&v_img[v_img_off(srow, schunk + 32)]) = vb4;  \
-    *reinterpret_cast<uint4*>(&v_img[v_img_off(srow, schunk + 40)]) = vb5;  \
-    *reinterpret_cast<uint4*>(&v_img[v_img_off(srow, schunk + 48)]) = vb6;  \
-    *reinterpret_cast<uint4*>(&v_img[v_img_off(srow, schunk + 56)]) = vb7;  \
-  } while (0)
-
-  float m[4], l[4];
-  f32x4 acc_o[8];
+// Online softmax of the page pair starting at page pg: the lane holds rows
+// 4*gslice+r for key cols (pg*16+gl, pg*16+16+gl); ONE group16 round covers
+// both pages.  Rescales acc_o and leaves P (bf16) in p_lds.
+DEV_INLINE void pair_softmax(const f32x4& sA, const f32x4& sB, float scale,
+                             int pg, const SplitRange& sr, float (&m)[4],
+                             float (&l)[4], f32x4 (&acc_o)[8],
+                             __hip_bfloat16* p_lds, int gl, int gslice) {
+  const int keyA = pg * 16 + gl;
+  const int keyB = keyA + 16;
+  const bool vA = keyA >= sr.key_begin && keyA < sr.key_end;
+  const bool vB = keyB >= sr.key_begin && keyB < sr.key_end;
+  float pA[4], pB[4];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) { m[r] = NEG_INF; l[r] = 0.f; }
+  for (int r = 0; r < 4; ++r) {
+    const float a = vA ? sA[r] * scale : NEG_INF;
+    const float b = vB ? sB[r] * scale : NEG_INF;
+    const float tm = group16_max(fmaxf(a, b));
+    const float m_new = fmaxf(m[r], tm);
+    const float alpha = __expf(m[r] - m_new);
+    pA[r] = vA ? __expf(a - m_new) : 0.f;
+    pB[r] = vB ? __expf(b - m_new) : 0.f;
+    l[r] = l[r] * alpha + group16_sum(pA[r] + pB[r]);
+    m[r] = m_new;
 #pragma unroll
-  for (int dt = 0; dt < 8; ++dt) acc_o[dt] = {0.f, 0.f, 0.f, 0.f};
-
-  DM_ISSUE_K(pg_begin);
-
-  for (int pg = pg_begin; pg < pg_end; pg += 2) {
-    // DIET: reload q fragments BEFORE the V issue, so the dependency wait
-    // in front of the first S MFMA is vmcnt(8) — V keeps streaming
-    dm_bf8 qd[4];
-    if constexpr (DIET) {
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        union { uint4 u; dm_bf8 v; } cvt;
-        cvt.u = *reinterpret_cast<const uint4*>(qrow + ks * 32 + gslice * 8);
-        qd[ks] = cvt.v;
-      }
-    }
-    DM_WRITE_K();
-    uint4 vb0, vb1, vb2, vb3, vb4, vb5, vb6, vb7;
-    if constexpr (!DIET) DM_ISSUE_V(pg);  // V hides under S + softmax
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-
-    // S = q K^T over the pair's 32 keys (B-frag: key row = gl / gl+16)
-    f32x4 sA = {0.f, 0.f, 0.f, 0.f}, sB = sA;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      union { uint4 u; dm_bf8 v; } kfA, kfB;
-      kfA.u = *reinterpret_cast<const uint4*>(
-          &k_lds[gl * KP + ks * 32 + gslice * 8]);
-      kfB.u = *reinterpret_cast<const uint4*>(
-          &k_lds[(16 + gl) * KP + ks * 32 + gslice * 8]);
-      const dm_bf8 qk = DIET ? qd[ks] : qa[ks];
-      sA = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qk, kfA.v, sA, 0, 0, 0);
-      sB = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qk, kfB.v, sB, 0, 0, 0);
-    }
-    // DIET: q fragments are dead now — V stages into their registers and
-    // its latency hides under the softmax shuffle chain below
-    if constexpr (DIET) DM_ISSUE_V_D(pg);
-
-    // online softmax: lane holds rows 4*gslice+r for key cols
-    // (pg*16+gl, pg*16+16+gl); ONE group16 round covers both pages
-    const int keyA = pg * 16 + gl;
-    const int keyB = keyA + 16;
-    const bool vA = keyA >= key_begin && keyA < key_end;
-    const bool vB = keyB >= key_begin && keyB < key_end;
-    float pA[4], pB[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float a = vA ? sA[r] * scale : NEG_INF;
-      const float b = vB ? sB[r] * scale : NEG_INF;
-      const float tm = group16_max(fmaxf(a, b));
-      const float m_new = fmaxf(m[r], tm);
-      const float alpha = __expf(m[r] - m_new);
-      pA[r] = vA ? __expf(a - m_new) : 0.f;
-      pB[r] = vB ? __expf(b - m_new) : 0.f;
-      l[r] = l[r] * alpha + group16_sum(pA[r] + pB[r]);
-      m[r] = m_new;
-      acc_o[0][r] *= alpha; acc_o[1][r] *= alpha;
-      acc_o[2][r] *= alpha; acc_o[3][r] *= alpha;
-      acc_o[4][r] *= alpha; acc_o[5][r] *= alpha;
-      acc_o[6][r] *= alpha; acc_o[7][r] *= alpha;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      p_lds[(4 * gslice + r) * 40 + gl] = f2bf(pA[r]);
-      p_lds[(4 * gslice + r) * 40 + 16 + gl] = f2bf(pB[r]);
-    }
-    // V overwrites the K panel: same-wave DS ordering protects the S
-    // fragment reads issued above
-    if constexpr (DIET) DM_WRITE_V_D();
-    else DM_WRITE_V();
-    DM_ISSUE_K(pg + 2);      // next pair's K hides under PV
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-
-    // O += P V via the 32-k fragment + tr-read V image (attn_prefill PV)
-    if constexpr (!DIET) {
-      union { uint4 u; dm_bf8 v; } paf;
-      const int pk = gslice * 8;
-      paf.u.x = *reinterpret_cast<const uint*>(&p_lds[gl * 40 + pk]);
-      paf.u.y = *reinterpret_cast<const uint*>(&p_lds[gl * 40 + pk + 2]);
-      paf.u.z = *reinterpret_cast<const uint*>(&p_lds[gl * 40 + pk + 4]);
-      paf.u.w = *reinterpret_cast<const uint*>(&p_lds[gl * 40 + pk + 6]);
-      const unsigned vaddr = (unsigned)(unsigned long long)(
-          &v_img[gslice * 64 + gl * 4]);
-      unsigned long long vlo[8], vhi[8];
-      asm volatile(
-          "ds_read_b64_tr_b16 %0, %16\n\t"
-          "ds_read_b64_tr_b16 %1, %16 offset:512\n\t"
-          "ds_read_b64_tr_b16 %2, %16 offset:1024\n\t"
-          "ds_read_b64_tr_b16 %3, %16 offset:1536\n\t"
-          "ds_read_b64_tr_b16 %4, %16 offset:2048\n\t"
-          "ds_read_b64_tr_b16 %5, %16 offset:2560\n\t"
-          "ds_read_b64_tr_b16 %6, %16 offset:3072\n\t"
-          "ds_read_b64_tr_b16 %7, %16 offset:3584\n\t"
-          "ds_read_b64_tr_b16 %8, %16 offset:4096\n\t"
-          "ds_read_b64_tr_b16 %9, %16 offset:4608\n\t"
-          "ds_read_b64_tr_b16 %10, %16 offset:5120\n\t"
-          "ds_read_b64_tr_b16 %11, %16 offset:5632\n\t"
-          "ds_read_b64_tr_b16 %12, %16 offset:6144\n\t"
-          "ds_read_b64_tr_b16 %13, %16 offset:6656\n\t"
-          "ds_read_b64_tr_b16 %14, %16 offset:7168\n\t"
-          "ds_read_b64_tr_b16 %15, %16 offset:7680\n\t"
-          "s_waitcnt lgkmcnt(0)"
-          : "=&v"(vlo[0]), "=&v"(vhi[0]), "=&v"(vlo[1]), "=&v"(vhi[1]),
-            "=&v"(vlo[2]), "=&v"(vhi[2]), "=&v"(vlo[3]), "=&v"(vhi[3]),
-            "=&v"(vlo[4]), "=&v"(vhi[4]), "=&v"(vlo[5]), "=&v"(vhi[5]),
-            "=&v"(vlo[6]), "=&v"(vhi[6]), "=&v"(vlo[7]), "=&v"(vhi[7])
-          : "v"(vaddr)
-          : "memory");
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int dt = 0; dt < 8; ++dt) {
-        union { struct { unsigned long long lo, hi; } u; dm_bf8 vf2; } vf;
-        vf.u.lo = vlo[dt];
-        vf.u.hi = vhi[dt];
-        acc_o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            paf.v, vf.vf2, acc_o[dt], 0, 0, 0);
-      }
-    } else {
-      // DIET PV: two 4-dt halves so only 16 tr-read VGPRs are live at a
-      // time (the full 32-reg batch overlapped the 32 in-flight K staging
-      // registers and was the register-pressure peak)
-      union { uint4 u; dm_bf8 v; } paf;
-      const int pk = gslice * 8;
-      paf.u.x = *reinterpret_cast<const uint*>(&p_lds[gl * 40 + pk]);
-      paf.u.y = *reinterpret_cast<const uint*>(&p_lds[gl * 40 + pk + 2]);
-      paf.u.z = *reinterpret_cast<const uint*>(&p_lds[gl * 40 + pk + 4]);
-      paf.u.w = *reinterpret_cast<const uint*>(&p_lds[gl * 40 + pk + 6]);
-      const unsigned vaddr = (unsigned)(unsigned long long)(
-          &v_img[gslice * 64 + gl * 4]);
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        unsigned long long vlo[4], vhi[4];
-        if (half == 0) {
-          asm volatile(
-              "ds_read_b64_tr_b16 %0, %8\n\t"
-              "ds_read_b64_tr_b16 %1, %8 offset:512\n\t"
-              "ds_read_b64_tr_b16 %2, %8 offset:1024\n\t"
-              "ds_read_b64_tr_b16 %3, %8 offset:1536\n\t"
-              "ds_read_b64_tr_b16 %4, %8 offset:2048\n\t"
-              "ds_read_b64_tr_b16 %5, %8 offset:2560\n\t"
-              "ds_read_b64_tr_b16 %6, %8 offset:3072\n\t"
-              "ds_read_b64_tr_b16 %7, %8 offset:3584\n\t"
-              "s_waitcnt lgkmcnt(0)"
-              : "=&v"(vlo[0]), "=&v"(vhi[0]), "=&v"(vlo[1]), "=&v"(vhi[1]),
-                "=&v"(vlo[2]), "=&v"(vhi[2]), "=&v"(vlo[3]), "=&v"(vhi[3])
-              : "v"(vaddr)
-              : "memory");
-        } else {
-          asm volatile(
-              "ds_read_b64_tr_b16 %0, %8 offset:4096\n\t"
-              "ds_read_b64_tr_b16 %1, %8 offset:4608\n\t"
-              "ds_read_b64_tr_b16 %2, %8 offset:5120\n\t"
-              "ds_read_b64_tr_b16 %3, %8 offset:5632\n\t"
-              "ds_read_b64_tr_b16 %4, %8 offset:6144\n\t"
-              "ds_read_b64_tr_b16 %5, %8 offset:6656\n\t"
-              "ds_read_b64_tr_b16 %6, %8 offset:7168\n\t"
-              "ds_read_b64_tr_b16 %7, %8 offset:7680\n\t"
-              "s_waitcnt lgkmcnt(0)"
-              : "=&v"(vlo[0]), "=&v"(vhi[0]), "=&v"(vlo[1]), "=&v"(vhi[1]),
-                "=&v"(vlo[2]), "=&v"(vhi[2]), "=&v"(vlo[3]), "=&v"(vhi[3])
-              : "v"(vaddr)
-              : "memory");
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-          union { struct { unsigned long long lo, hi; } u; dm_bf8 vf2; } vf;
-          vf.u.lo = vlo[dt];
-          vf.u.hi = vhi[dt];
-          acc_o[half * 4 + dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              paf.v, vf.vf2, acc_o[half * 4 + dt], 0, 0, 0);
-        }
-      }
-    }
+    for (int dt = 0; dt < 8; ++dt) acc_o[dt][r] *= alpha;
   }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    p_lds[(4 * gslice + r) * DM_PP + gl] = f2bf(pA[r]);
+    p_lds[(4 * gslice + r) * DM_PP + 16 + gl] = f2bf(pB[r]);
+  }
+}
 
-  // epilogue: lane holds O rows 4*gslice+r at dim cols dt*16+gl
+// P A-fragment of the pair: row = gl, the lane's 8 keys from gslice*8
+DEV_INLINE bf8 load_p_frag(const __hip_bfloat16* p_lds, int gl, int gslice) {
+  union { uint4 u; bf8 v; } paf;
+  const __hip_bfloat16* p = &p_lds[gl * DM_PP + gslice * 8];
+  paf.u.x = *reinterpret_cast<const uint*>(p);
+  paf.u.y = *reinterpret_cast<const uint*>(p + 2);
+  paf.u.z = *reinterpret_cast<const uint*>(p + 4);
+  paf.u.w = *reinterpret_cast<const uint*>(p + 6);
+  return paf.v;
+}
+
+// Epilogue: the lane holds O rows 4*gslice+r at dim cols dt*16+gl.  One
+// split writes the normalised output, more write (O, m, l) partials.
+template <int QPG>
+DEV_INLINE void store_pair_output(float* partial_o, float* partial_ml,
+                                  __hip_bfloat16* out,
+                                  const f32x4 (&acc_o)[8], const float (&m)[4],
+                                  const float (&l)[4], int seq, int num_seqs,
+                                  int split, int num_splits, int kvh,
+                                  int num_kv_heads, int gl, int gslice) {
+  const int num_q_heads = num_kv_heads * QPG;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int row = 4 * gslice + r;
@@ -669,6 +421,154 @@ __global__ __launch_bounds__(128, DIET ? 4 : 3) void decode_attn_mfma_kernel(
       }
     }
   }
+}
+
+// Global -> LDS staging of one page pair.  The lane covers K/V key row
+// srow = lane>>1 (32 rows: page myloc = srow>>4 of the pair) and the 64-elem
+// chunk schunk = (lane&1)*64, i.e. 8 x 16 B pieces; 2 lanes x 128 B = one
+// contiguous page row.  The pieces live in NAMED SCALAR registers R0..R7
+// (docs/cdna_lessons.md §1: local arrays are demoted to scratch memory,
+// round-tripping every staged page via HBM).  The macros use the kernel's
+// btab, pg_last, srow, schunk, myloc, k_lds and v_img.  Pages past the
+// split clamp to its last real page (pg_last, itself clamped at 0 so a
+// ctx == 0 row reads btab[0], never btab[-1]).
+#define DM_REGS(R) uint4 R##0, R##1, R##2, R##3, R##4, R##5, R##6, R##7
+#define DM_ISSUE(cache, R, pg)                                              \
+  do {                                                                      \
+    const int p_ = btab[min((pg) + myloc, pg_last)];                        \
+    const __hip_bfloat16* src_ = (cache) + schunk +                         \
+        (((size_t)p_ * num_kv_heads + kvh) * 16 + (srow & 15)) * HEAD_DIM;  \
+    R##0 = *reinterpret_cast<const uint4*>(src_);                           \
+    R##1 = *reinterpret_cast<const uint4*>(src_ + 8);                       \
+    R##2 = *reinterpret_cast<const uint4*>(src_ + 16);                      \
+    R##3 = *reinterpret_cast<const uint4*>(src_ + 24);                      \
+    R##4 = *reinterpret_cast<const uint4*>(src_ + 32);                      \
+    R##5 = *reinterpret_cast<const uint4*>(src_ + 40);                      \
+    R##6 = *reinterpret_cast<const uint4*>(src_ + 48);                      \
+    R##7 = *reinterpret_cast<const uint4*>(src_ + 56);                      \
+  } while (0)
+#define DM_K_AT(c) (&k_lds[srow * DM_KP + schunk + (c)])
+#define DM_V_AT(c) (&v_img[v_img_off(srow, schunk + (c))])
+#define DM_WRITE(R, AT)                                                     \
+  do {                                                                      \
+    *reinterpret_cast<uint4*>(AT(0)) = R##0;                                \
+    *reinterpret_cast<uint4*>(AT(8)) = R##1;                                \
+    *reinterpret_cast<uint4*>(AT(16)) = R##2;                               \
+    *reinterpret_cast<uint4*>(AT(24)) = R##3;                               \
+    *reinterpret_cast<uint4*>(AT(32)) = R##4;                               \
+    *reinterpret_cast<uint4*>(AT(40)) = R##5;                               \
+    *reinterpret_cast<uint4*>(AT(48)) = R##6;                               \
+    *reinterpret_cast<uint4*>(AT(56)) = R##7;                               \
+  } while (0)
+
+// One wave per sequence (variant 4; DIET = variant 5), two sequences per
+// 2-wave workgroup, 19 KB LDS per workgroup.  MFMA depth inside the wave
+// covers the low waves/SIMD (the same budget shape as the 8-wave prefill
+// kernel).
+// DIET: the round-2 register diet targeting 4 waves/SIMD
+// (docs/ROUND2_DESIGNS.md §1a+1b).  Two changes vs variant 4:
+//  (a) q fragments are RELOADED from global per page pair instead of held
+//      in 16 persistent VGPRs — the rows are the same cache lines every
+//      pair, so after the first touch they come from L1.  Issued BEFORE
+//      the V stage so the compiler's dependency waitcnt for the first S
+//      MFMA is vmcnt(8) (V still in flight), not a pipeline drain.
+//  (b) V issues AFTER the S MFMAs, when the q fragments are dead, so the
+//      allocator colors V's staging registers into theirs, and PV runs in
+//      two 4-tile halves (PV_STEP8) so only 16 tr-read VGPRs are live at a
+//      time.  The round-67 FULL merge (one 8-set for K and V) hit in-loop
+//      spills and lost 27%.
+// The diet does not fit 128 VGPRs cleanly: with the compiler in this tree all
+// four DIET instantiations spill (36-60 B of scratch per lane, see
+// profiles/attn_refactor_resources.txt); variant 4 has no scratch.
+template <int QPG, int DIET>
+__global__ __launch_bounds__(128, DIET ? 4 : 3) void decode_attn_mfma_kernel(
+    float* __restrict__ partial_o,        // [splits, seqs, QH, D]
+    float* __restrict__ partial_ml,       // [splits, seqs, QH, 2]
+    __hip_bfloat16* __restrict__ out,     // [seqs, QH, D] (splits==1 path)
+    const __hip_bfloat16* __restrict__ q, // [seqs, QH, D]
+    const __hip_bfloat16* __restrict__ key_cache,  // [pages, KVH, 16, D]
+    const __hip_bfloat16* __restrict__ val_cache,
+    const int* __restrict__ block_tables, // [seqs, max_pages]
+    const int* __restrict__ context_lens, // [seqs]
+    const float scale, const int num_kv_heads, const int max_pages,
+    const int num_splits, const int num_seqs, const int q_stride) {
+  const int kvh = blockIdx.x;
+  const int wave = threadIdx.x >> 6;
+  const int seq = blockIdx.y * 2 + wave;
+  const int split = blockIdx.z;
+  const int lane = threadIdx.x & 63;
+  const int gl = lane & 15;
+  const int gslice = lane >> 4;
+
+  // per-wave LDS (no cross-wave sharing, no barriers).  K and V SHARE one
+  // buffer: the pair's K panel serves the S MFMAs, then the V image
+  // overwrites it for PV (same-wave DS ops retire in order, so the
+  // write-after-read needs no fence) — halving LDS doubles resident
+  // waves.  V is fully rewritten every pair (tail pages clamp to real
+  // pages and are masked through P=0), so no zero-init is needed.
+  __shared__ __hip_bfloat16 kv_all[2][32 * DM_KP];  // K panel / V tr image
+  __shared__ __hip_bfloat16 p_lds_all[2][16 * DM_PP];
+  __hip_bfloat16* k_lds = kv_all[wave];
+  __hip_bfloat16* v_img = kv_all[wave];
+  __hip_bfloat16* p_lds = p_lds_all[wave];
+  if (seq >= num_seqs) return;
+  const SplitRange sr = split_range(context_lens[seq], split, num_splits);
+
+  // DIET: fragments reload per pair (L1)
+  const __hip_bfloat16* q_seq = q + (size_t)seq * q_stride;
+  bf8 qa[4];
+  if constexpr (!DIET) load_q_frags<QPG>(qa, q_seq, kvh, gl, gslice);
+
+  const int* btab = block_tables + (size_t)seq * max_pages;
+  const int srow = lane >> 1, schunk = (lane & 1) * 64, myloc = srow >> 4;
+  const int pg_last = max(sr.pg_end - 1, 0);
+  DM_REGS(ka);
+
+  float m[4], l[4];
+  f32x4 acc_o[8];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) { m[r] = NEG_INF; l[r] = 0.f; }
+#pragma unroll
+  for (int dt = 0; dt < 8; ++dt) acc_o[dt] = {0.f, 0.f, 0.f, 0.f};
+
+  DM_ISSUE(key_cache, ka, sr.pg_begin);
+
+  for (int pg = sr.pg_begin; pg < sr.pg_end; pg += 2) {
+    // DIET: reload q fragments BEFORE the V issue, so the dependency wait
+    // in front of the first S MFMA is vmcnt(8) — V keeps streaming
+    if constexpr (DIET) load_q_frags<QPG>(qa, q_seq, kvh, gl, gslice);
+    DM_WRITE(ka, DM_K_AT);
+    DM_REGS(va);
+    if constexpr (!DIET) DM_ISSUE(val_cache, va, pg);  // V hides under S
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+
+    f32x4 sA, sB;
+    score_pair(sA, sB, qa, k_lds, gl, gslice);
+    // DIET: q fragments are dead now — V stages into their registers and
+    // its latency hides under the softmax shuffle chain below
+    if constexpr (DIET) DM_ISSUE(val_cache, va, pg);
+
+    pair_softmax(sA, sB, scale, pg, sr, m, l, acc_o, p_lds, gl, gslice);
+    // V overwrites the K panel: same-wave DS ordering protects the S
+    // fragment reads issued above
+    DM_WRITE(va, DM_V_AT);
+    DM_ISSUE(key_cache, ka, pg + 2);      // next pair's K hides under PV
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+
+    // O += P V via the 32-k fragment + tr-read V image
+    const bf8 pa = load_p_frag(p_lds, gl, gslice);
+    const unsigned vaddr = v_img_lane_addr(v_img, gl, gslice);
+    if constexpr (!DIET) {
+      PV_STEP16(acc_o, pa, vaddr);
+    } else {
+      PV_STEP8(acc_o, pa, vaddr, 0);
+      PV_STEP8(acc_o, pa, vaddr, 1);
+    }
+  }
+
+  store_pair_output<QPG>(partial_o, partial_ml, out, acc_o, m, l, seq,
+                         num_seqs, split, num_splits, kvh, num_kv_heads, gl,
+                         gslice);
 }
 
 // ---------------------------------------------------------------------------
@@ -699,7 +599,6 @@ __global__ __launch_bounds__(128, 4) void decode_attn_pc_kernel(
     const int* __restrict__ context_lens, // [seqs]
     const float scale, const int num_kv_heads, const int max_pages,
     const int num_splits, const int num_seqs, const int q_stride) {
-  typedef __attribute__((ext_vector_type(8))) __bf16 dm_bf8;
   const int kvh = blockIdx.x;
   const int seq = blockIdx.y;
   const int split = blockIdx.z;
@@ -707,12 +606,10 @@ __global__ __launch_bounds__(128, 4) void decode_attn_pc_kernel(
   const int lane = threadIdx.x & 63;
   const int gl = lane & 15;
   const int gslice = lane >> 4;
-  const int num_q_heads = num_kv_heads * QPG;
 
-  constexpr int KP = 132;
-  __shared__ __hip_bfloat16 k_lds[32 * KP];
+  __shared__ __hip_bfloat16 k_lds[32 * DM_KP];
   __shared__ __hip_bfloat16 v_img[32 * 128];
-  __shared__ __hip_bfloat16 p_lds[16 * 40];
+  __shared__ __hip_bfloat16 p_lds[16 * DM_PP];
   __shared__ int flags[4];   // prod_k, prod_v, cons_s, cons_pv (pair idx)
   if (threadIdx.x == 0) {
     flags[0] = -1; flags[1] = -1; flags[2] = -1; flags[3] = -1;
@@ -723,75 +620,42 @@ __global__ __launch_bounds__(128, 4) void decode_attn_pc_kernel(
   volatile int* f_cons_s = &flags[2];
   volatile int* f_cons_pv = &flags[3];
 
-  const int ctx = context_lens[seq];
-  const int chunk = 16;
-  const int nchunks = (ctx + chunk - 1) / chunk;
-  const int per_split = (nchunks + num_splits - 1) / num_splits;
-  const int key_begin = split * per_split * chunk;
-  const int key_end = min(ctx, (split + 1) * per_split * chunk);
-  const int pg_begin = key_begin >> 4;
-  const int pg_end = (key_end + 15) >> 4;
-  const int npairs = max(0, (pg_end - pg_begin + 1) >> 1);
-
-  const int* btab = block_tables + (size_t)seq * max_pages;
-  // for empty splits the clamp keeps block-table reads at the last REAL
-  // page (same convention as variant 4); ctx == 0 gives npairs == 0 and
-  // pg_end == 0, so pg_last clamps at 0
-  const int pg_last = max(pg_end - 1, 0);
+  const SplitRange sr = split_range(context_lens[seq], split, num_splits);
+  const int npairs = max(0, (sr.pg_end - sr.pg_begin + 1) >> 1);
 
 #define PC_SPIN(fl, want)                                                    \
   while (*(fl) < (want)) __builtin_amdgcn_s_sleep(2)
 
   if (wave == 1) {
     // ---- producer -------------------------------------------------------
-    const int srow = lane >> 1, schunk = (lane & 1) * 64;
-    const int myloc = srow >> 4;
-    auto page_base = [&](int pg, int local) -> size_t {
-      const int p = btab[min(pg + local, pg_last)];
-      return (((size_t)p * num_kv_heads + kvh) * 16 + (srow & 15)) *
-                 HEAD_DIM + schunk;
-    };
-    uint4 ka0, ka1, ka2, ka3, ka4, ka5, ka6, ka7;
-    uint4 va0, va1, va2, va3, va4, va5, va6, va7;
+    const int* btab = block_tables + (size_t)seq * max_pages;
+    const int srow = lane >> 1, schunk = (lane & 1) * 64, myloc = srow >> 4;
+    const int pg_last = max(sr.pg_end - 1, 0);
+    DM_REGS(ka);
+    DM_REGS(va);
     if (npairs > 0) {
-      DM_LOAD8(key_cache, ka0, ka1, ka2, ka3, ka4, ka5, ka6, ka7,
-               page_base(pg_begin, myloc));
-      DM_LOAD8(val_cache, va0, va1, va2, va3, va4, va5, va6, va7,
-               page_base(pg_begin, myloc));
+      DM_ISSUE(key_cache, ka, sr.pg_begin);
+      DM_ISSUE(val_cache, va, sr.pg_begin);
     }
     for (int i = 0; i < npairs; ++i) {
-      const int pg_next = pg_begin + 2 * (i + 1);
+      const int pg_next = sr.pg_begin + 2 * (i + 1);
       PC_SPIN(f_cons_s, i - 1);          // K panel free
-      DM_WRITE_K();
+      DM_WRITE(ka, DM_K_AT);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       if (lane == 0) *f_prod_k = i;
-      if (i + 1 < npairs)
-        DM_LOAD8(key_cache, ka0, ka1, ka2, ka3, ka4, ka5, ka6, ka7,
-                 page_base(pg_next, myloc));
+      if (i + 1 < npairs) DM_ISSUE(key_cache, ka, pg_next);
       PC_SPIN(f_cons_pv, i - 1);         // V image free
-      DM_WRITE_V();
+      DM_WRITE(va, DM_V_AT);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       if (lane == 0) *f_prod_v = i;
-      if (i + 1 < npairs)
-        DM_LOAD8(val_cache, va0, va1, va2, va3, va4, va5, va6, va7,
-                 page_base(pg_next, myloc));
+      if (i + 1 < npairs) DM_ISSUE(val_cache, va, pg_next);
     }
     return;
   }
 
   // ---- consumer ---------------------------------------------------------
-  dm_bf8 qa[4];
-  {
-    const __hip_bfloat16* qrow =
-        q + (size_t)seq * q_stride +
-        (size_t)(kvh * QPG + min(gl, QPG - 1)) * HEAD_DIM;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      union { uint4 u; dm_bf8 v; } cvt;
-      cvt.u = *reinterpret_cast<const uint4*>(qrow + ks * 32 + gslice * 8);
-      qa[ks] = cvt.v;
-    }
-  }
+  bf8 qa[4];
+  load_q_frags<QPG>(qa, q + (size_t)seq * q_stride, kvh, gl, gslice);
   float m[4], l[4];
   f32x4 acc_o[8];
 #pragma unroll
@@ -800,135 +664,35 @@ __global__ __launch_bounds__(128, 4) void decode_attn_pc_kernel(
   for (int dt = 0; dt < 8; ++dt) acc_o[dt] = {0.f, 0.f, 0.f, 0.f};
 
   for (int i = 0; i < npairs; ++i) {
-    const int pg = pg_begin + 2 * i;
     PC_SPIN(f_prod_k, i);
-    f32x4 sA = {0.f, 0.f, 0.f, 0.f}, sB = sA;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      union { uint4 u; dm_bf8 v; } kfA, kfB;
-      kfA.u = *reinterpret_cast<const uint4*>(
-          &k_lds[gl * KP + ks * 32 + gslice * 8]);
-      kfB.u = *reinterpret_cast<const uint4*>(
-          &k_lds[(16 + gl) * KP + ks * 32 + gslice * 8]);
-      sA = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[ks], kfA.v, sA, 0, 0, 0);
-      sB = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[ks], kfB.v, sB, 0, 0, 0);
-    }
+    f32x4 sA, sB;
+    score_pair(sA, sB, qa, k_lds, gl, gslice);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // frag reads done
     if (lane == 0) *f_cons_s = i;        // K panel may be overwritten
 
-    const int keyA = pg * 16 + gl;
-    const int keyB = keyA + 16;
-    const bool vA = keyA >= key_begin && keyA < key_end;
-    const bool vB = keyB >= key_begin && keyB < key_end;
-    float pA[4], pB[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float a = vA ? sA[r] * scale : NEG_INF;
-      const float b = vB ? sB[r] * scale : NEG_INF;
-      const float tm = group16_max(fmaxf(a, b));
-      const float m_new = fmaxf(m[r], tm);
-      const float alpha = __expf(m[r] - m_new);
-      pA[r] = vA ? __expf(a - m_new) : 0.f;
-      pB[r] = vB ? __expf(b - m_new) : 0.f;
-      l[r] = l[r] * alpha + group16_sum(pA[r] + pB[r]);
-      m[r] = m_new;
-      acc_o[0][r] *= alpha; acc_o[1][r] *= alpha;
-      acc_o[2][r] *= alpha; acc_o[3][r] *= alpha;
-      acc_o[4][r] *= alpha; acc_o[5][r] *= alpha;
-      acc_o[6][r] *= alpha; acc_o[7][r] *= alpha;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      p_lds[(4 * gslice + r) * 40 + gl] = f2bf(pA[r]);
-      p_lds[(4 * gslice + r) * 40 + 16 + gl] = f2bf(pB[r]);
-    }
+    pair_softmax(sA, sB, scale, sr.pg_begin + 2 * i, sr, m, l, acc_o, p_lds,
+                 gl, gslice);
 
     PC_SPIN(f_prod_v, i);
-    {
-      union { uint4 u; dm_bf8 v; } paf;
-      const int pk = gslice * 8;
-      paf.u.x = *reinterpret_cast<const uint*>(&p_lds[gl * 40 + pk]);
-      paf.u.y = *reinterpret_cast<const uint*>(&p_lds[gl * 40 + pk + 2]);
-      paf.u.z = *reinterpret_cast<const uint*>(&p_lds[gl * 40 + pk + 4]);
-      paf.u.w = *reinterpret_cast<const uint*>(&p_lds[gl * 40 + pk + 6]);
-      const unsigned vaddr = (unsigned)(unsigned long long)(
-          &v_img[gslice * 64 + gl * 4]);
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        unsigned long long vlo[4], vhi[4];
-        if (half == 0) {
-          asm volatile(
-              "ds_read_b64_tr_b16 %0, %8\n\t"
-              "ds_read_b64_tr_b16 %1, %8 offset:512\n\t"
-              "ds_read_b64_tr_b16 %2, %8 offset:1024\n\t"
-              "ds_read_b64_tr_b16 %3, %8 offset:1536\n\t"
-              "ds_read_b64_tr_b16 %4, %8 offset:2048\n\t"
-              "ds_read_b64_tr_b16 %5, %8 offset:2560\n\t"
-              "ds_read_b64_tr_b16 %6, %8 offset:3072\n\t"
-              "ds_read_b64_tr_b16 %7, %8 offset:3584\n\t"
-              "s_waitcnt lgkmcnt(0)"
-              : "=&v"(vlo[0]), "=&v"(vhi[0]), "=&v"(vlo[1]), "=&v"(vhi[1]),
-                "=&v"(vlo[2]), "=&v"(vhi[2]), "=&v"(vlo[3]), "=&v"(vhi[3])
-              : "v"(vaddr)
-              : "memory");
-        } else {
-          asm volatile(
-              "ds_read_b64_tr_b16 %0, %8 offset:4096\n\t"
-              "ds_read_b64_tr_b16 %1, %8 offset:4608\n\t"
-              "ds_read_b64_tr_b16 %2, %8 offset:5120\n\t"
-              "ds_read_b64_tr_b16 %3, %8 offset:5632\n\t"
-              "ds_read_b64_tr_b16 %4, %8 offset:6144\n\t"
-              "ds_read_b64_tr_b16 %5, %8 offset:6656\n\t"
-              "ds_read_b64_tr_b16 %6, %8 offset:7168\n\t"
-              "ds_read_b64_tr_b16 %7, %8 offset:7680\n\t"
-              "s_waitcnt lgkmcnt(0)"
-              : "=&v"(vlo[0]), "=&v"(vhi[0]), "=&v"(vlo[1]), "=&v"(vhi[1]),
-                "=&v"(vlo[2]), "=&v"(vhi[2]), "=&v"(vlo[3]), "=&v"(vhi[3])
-              : "v"(vaddr)
-              : "memory");
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-          union { struct { unsigned long long lo, hi; } u; dm_bf8 vf2; } vf;
-          vf.u.lo = vlo[dt];
-          vf.u.hi = vhi[dt];
-          acc_o[half * 4 + dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              paf.v, vf.vf2, acc_o[half * 4 + dt], 0, 0, 0);
-        }
-      }
-    }
+    const bf8 pa = load_p_frag(p_lds, gl, gslice);
+    const unsigned vaddr = v_img_lane_addr(v_img, gl, gslice);
+    PV_STEP8(acc_o, pa, vaddr, 0);
+    PV_STEP8(acc_o, pa, vaddr, 1);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (lane == 0) *f_cons_pv = i;       // V image may be overwritten
   }
 #undef PC_SPIN
 
-  // epilogue identical to variant 4
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int row = 4 * gslice + r;
-    if (row >= QPG) continue;
-    const int qh = kvh * QPG + row;
-    if (num_splits == 1) {
-      const float inv_l = l[r] > 0.f ? 1.f / l[r] : 0.f;
-#pragma unroll
-      for (int dt = 0; dt < 8; ++dt)
-        out[((size_t)seq * num_q_heads + qh) * HEAD_DIM + dt * 16 + gl] =
-            f2bf(acc_o[dt][r] * inv_l);
-    } else {
-#pragma unroll
-      for (int dt = 0; dt < 8; ++dt)
-        partial_o[(((size_t)split * num_seqs + seq) * num_q_heads + qh) *
-                      HEAD_DIM + dt * 16 + gl] = acc_o[dt][r];
-      if (gl == 0) {
-        float* ml = partial_ml +
-            (((size_t)split * num_seqs + seq) * num_q_heads + qh) * 2;
-        ml[0] = m[r];
-        ml[1] = l[r];
-      }
-    }
-  }
+  store_pair_output<QPG>(partial_o, partial_ml, out, acc_o, m, l, seq,
+                         num_seqs, split, num_splits, kvh, num_kv_heads, gl,
+                         gslice);
 }
+
+#undef DM_REGS
+#undef DM_ISSUE
+#undef DM_K_AT
+#undef DM_V_AT
+#undef DM_WRITE
 
 // Merge split partials: one block per (seq, q_head).
 __global__ void decode_combine_kernel(
@@ -955,6 +719,27 @@ __global__ void decode_combine_kernel(
       f2bf(lsum > 0.f ? o / lsum : 0.f);
 }
 
+// Every decode kernel takes 8 pointers, the scale and 5 ints; only the
+// meaning of the middle ints differs (see launch_decode_attention).
+typedef void (*DecodeKernel)(float*, float*, __hip_bfloat16*,
+                             const __hip_bfloat16*, const __hip_bfloat16*,
+                             const __hip_bfloat16*, const int*, const int*,
+                             float, int, int, int, int, int);
+
+template <int QPG>
+DecodeKernel decode_kernel(int variant) {
+  switch (variant) {
+    case 0: return decode_attn_kernel<QPG, 0>;
+    case 1: return decode_attn_kernel<QPG, 1>;
+    case 2: return decode_attn_kernel<QPG, 2>;
+    case 3: return decode_attn_kernel<QPG, 3>;
+    case 4: return decode_attn_mfma_kernel<QPG, 0>;
+    case 5: return decode_attn_mfma_kernel<QPG, 1>;
+    case 6: return decode_attn_pc_kernel<QPG>;
+    default: return nullptr;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -967,97 +752,31 @@ void launch_decode_attention(void* out, void* partial_o, void* partial_ml,
                              int page_size, int max_pages, int num_splits,
                              int variant, int q_stride, hipStream_t stream) {
   const int qpg = num_q_heads / num_kv_heads;
-  dim3 grid(num_kv_heads, num_seqs, num_splits), block(256);
-#define LAUNCH_QPG(QPG, VAR)                                                  \
-  hipLaunchKernelGGL((decode_attn_kernel<QPG, VAR>), grid, block, 0, stream,  \
-                     (float*)partial_o, (float*)partial_ml,                   \
-                     (__hip_bfloat16*)out, (const __hip_bfloat16*)q,          \
-                     (const __hip_bfloat16*)key_cache,                        \
-                     (const __hip_bfloat16*)val_cache,                        \
-                     (const int*)block_tables, (const int*)context_lens,      \
-                     scale, num_kv_heads, page_size, max_pages, num_splits,  \
-                     q_stride)
-  if (variant == 6 && page_size == 16) {
-    dim3 pgrid(num_kv_heads, num_seqs, num_splits), pblock(128);
-#define LAUNCH_PC(QPG)                                                       \
-    hipLaunchKernelGGL((decode_attn_pc_kernel<QPG>), pgrid, pblock, 0,       \
-                       stream, (float*)partial_o, (float*)partial_ml,        \
-                       (__hip_bfloat16*)out, (const __hip_bfloat16*)q,       \
-                       (const __hip_bfloat16*)key_cache,                     \
-                       (const __hip_bfloat16*)val_cache,                     \
-                       (const int*)block_tables, (const int*)context_lens,   \
-                       scale, num_kv_heads, max_pages, num_splits,           \
-                       num_seqs, q_stride)
-    if (qpg == 1) LAUNCH_PC(1);
-    else if (qpg == 2) LAUNCH_PC(2);
-    else if (qpg == 4) LAUNCH_PC(4);
-    else if (qpg == 8) LAUNCH_PC(8);
-    else return;
-#undef LAUNCH_PC
-    if (num_splits > 1) {
-      dim3 cgrid(num_seqs, num_q_heads), cblock(HEAD_DIM);
-      hipLaunchKernelGGL(decode_combine_kernel, cgrid, cblock, 0, stream,
-                         (__hip_bfloat16*)out, (const float*)partial_o,
-                         (const float*)partial_ml, num_splits, num_q_heads);
-    }
-    return;
-  }
-  if ((variant == 4 || variant == 5) && page_size == 16) {
-    dim3 mgrid(num_kv_heads, (num_seqs + 1) / 2, num_splits), mblock(128);
-#define LAUNCH_MFMA(QPG, DIET)                                               \
-    hipLaunchKernelGGL((decode_attn_mfma_kernel<QPG, DIET>), mgrid, mblock,  \
-                       0,                                                    \
-                       stream, (float*)partial_o, (float*)partial_ml,        \
-                       (__hip_bfloat16*)out, (const __hip_bfloat16*)q,       \
-                       (const __hip_bfloat16*)key_cache,                     \
-                       (const __hip_bfloat16*)val_cache,                     \
-                       (const int*)block_tables, (const int*)context_lens,   \
-                       scale, num_kv_heads, max_pages, num_splits,         \
-                       num_seqs, q_stride)
-    if (variant == 5) {
-      if (qpg == 1) LAUNCH_MFMA(1, 1);
-      else if (qpg == 2) LAUNCH_MFMA(2, 1);
-      else if (qpg == 4) LAUNCH_MFMA(4, 1);
-      else if (qpg == 8) LAUNCH_MFMA(8, 1);
-      else return;
-    } else {
-      if (qpg == 1) LAUNCH_MFMA(1, 0);
-      else if (qpg == 2) LAUNCH_MFMA(2, 0);
-      else if (qpg == 4) LAUNCH_MFMA(4, 0);
-      else if (qpg == 8) LAUNCH_MFMA(8, 0);
-      else return;
-    }
-#undef LAUNCH_MFMA
-    if (num_splits > 1) {
-      dim3 cgrid(num_seqs, num_q_heads), cblock(HEAD_DIM);
-      hipLaunchKernelGGL(decode_combine_kernel, cgrid, cblock, 0, stream,
-                         (__hip_bfloat16*)out, (const float*)partial_o,
-                         (const float*)partial_ml, num_splits, num_q_heads);
-    }
-    return;
-  }
-  // variant 4 with a non-16 page size falls back to the dot2 kernel
-  const int v = variant < 0 ? 1 : (variant > 3 ? 1 : variant);
-  switch (qpg * 8 + v) {
-    case 8: LAUNCH_QPG(1, 0); break;
-    case 9: LAUNCH_QPG(1, 1); break;
-    case 10: LAUNCH_QPG(1, 2); break;
-    case 11: LAUNCH_QPG(1, 3); break;
-    case 16: LAUNCH_QPG(2, 0); break;
-    case 17: LAUNCH_QPG(2, 1); break;
-    case 18: LAUNCH_QPG(2, 2); break;
-    case 19: LAUNCH_QPG(2, 3); break;
-    case 32: LAUNCH_QPG(4, 0); break;
-    case 33: LAUNCH_QPG(4, 1); break;
-    case 34: LAUNCH_QPG(4, 2); break;
-    case 35: LAUNCH_QPG(4, 3); break;
-    case 64: LAUNCH_QPG(8, 0); break;
-    case 65: LAUNCH_QPG(8, 1); break;
-    case 66: LAUNCH_QPG(8, 2); break;
-    case 67: LAUNCH_QPG(8, 3); break;
-    default: return;   // validated host-side
-  }
-#undef LAUNCH_QPG
+  // the MFMA kernels need 16-token pages; otherwise, and for out-of-range
+  // variants, fall back to the dot2 kernel (variant 1)
+  const bool mfma = variant >= 4 && variant <= 6 && page_size == 16;
+  const int v = (mfma || (variant >= 0 && variant <= 3)) ? variant : 1;
+  const DecodeKernel kernel = qpg == 1   ? decode_kernel<1>(v)
+                              : qpg == 2 ? decode_kernel<2>(v)
+                              : qpg == 4 ? decode_kernel<4>(v)
+                              : qpg == 8 ? decode_kernel<8>(v)
+                                         : nullptr;
+  if (kernel == nullptr) return;   // validated host-side
+  // variants 4/5 pack two sequences (one per wave) into a workgroup
+  const int seq_blocks = (v == 4 || v == 5) ? (num_seqs + 1) / 2 : num_seqs;
+  const dim3 grid(num_kv_heads, seq_blocks, num_splits);
+  const dim3 block(mfma ? 128 : 256);
+  // int tail: dot2 (page_size, max_pages, num_splits),
+  //           MFMA (max_pages, num_splits, num_seqs)
+  hipLaunchKernelGGL(kernel, grid, block, 0, stream, (float*)partial_o,
+                     (float*)partial_ml, (__hip_bfloat16*)out,
+                     (const __hip_bfloat16*)q,
+                     (const __hip_bfloat16*)key_cache,
+                     (const __hip_bfloat16*)val_cache,
+                     (const int*)block_tables, (const int*)context_lens,
+                     scale, num_kv_heads, mfma ? max_pages : page_size,
+                     mfma ? num_splits : max_pages,
+                     mfma ? num_seqs : num_splits, q_stride);
   if (num_splits > 1) {
     dim3 cgrid(num_seqs, num_q_heads), cblock(HEAD_DIM);
     hipLaunchKernelGGL(decode_combine_kernel, cgrid, cblock, 0, stream,

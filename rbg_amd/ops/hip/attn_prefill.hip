@@ -15,69 +15,34 @@
 //
 // Capability analog: prefill attention of the engines the reference
 // orchestrates (SURVEY §2.3 prefill engine row).
-#include "common.h"
+#include "attn_mfma.h"
 
 namespace {
 
-constexpr int HEAD_DIM = 128;
 constexpr int KTILE = 64;      // keys per LDS tile
 constexpr int PAD = 8;         // bf16 row padding (16 B) — bank-conflict fix
-constexpr float NEG_INF = -1e30f;
 
-typedef __attribute__((ext_vector_type(8))) __bf16 mfma_bf8;
-typedef __attribute__((ext_vector_type(4))) float mfma_f4;
+// The (q block, q head) a workgroup computes.  grid: 1D, nblocks *
+// num_q_heads.  SWZ=1 remaps block ids so the QPG q-heads sharing one
+// (q-block, kv-head) K/V tile land on the SAME XCD (dispatcher places block
+// b on XCD b%8 — guide T1) temporally adjacent: the sharers then hit that
+// XCD's L2 instead of re-pulling HBM (the GQA staging re-read is the
+// dominant prefill cost, profiles/).
+struct PrefillBlock {
+  int qh, kvh;
+  // block_info row: q_offset is the position of q row 0 within the sequence
+  // (prefix caching / chunked prefill attend over [past; new] K/V)
+  int q_start, qblock, kv_start, q_offset;
+  int seq_len;                   // total KV tokens of the sequence
+};
 
-DEV_INLINE mfma_bf8 load_bf8(const __hip_bfloat16* p) {
-  union { uint4 u; mfma_bf8 v; } cvt;
-  cvt.u = *reinterpret_cast<const uint4*>(p);
-  return cvt.v;
-}
-
-DEV_INLINE mfma_bf8 lds_bf8(const __hip_bfloat16* p) {
-  union { uint4 u; mfma_bf8 v; } cvt;
-  cvt.u = *reinterpret_cast<const uint4*>(p);
-  return cvt.v;
-}
-
-// V image element offset for the ds_read_b64_tr_b16 PV path.  Per 32-key
-// step (ks) and 16-dim column tile (dt), a 16-lane group's [4 key][16 dim]
-// block lives at elems {q*64 + j*16 + d16} with the tr-read redistributing
-// it so lane l ends with keys q*8+half*4+j at its dim column (l&15) —
-// exactly the MFMA B-fragment (guide §2 tr-read layout; conflict-free
-// subtiling).  Writes land as contiguous 8-element (16 B) runs per
-// (key, 8-dim chunk), so staging stays fully vectorized.
-DEV_INLINE int v_img_off(int key, int dim) {
-  const int ks = key >> 5, kk = key & 31, q = kk >> 3, jj = kk & 7;
-  return ks * 4096 + (dim >> 4) * 512 + (jj >> 2) * 256 + q * 64 +
-         (jj & 3) * 16 + (dim & 15);
-}
-
-// grid: 1D, nblocks * num_q_heads.  SWZ=1 remaps block ids so the QPG
-// q-heads sharing one (q-block, kv-head) K/V tile land on the SAME XCD
-// (dispatcher places block b on XCD b%8 — guide T1) temporally adjacent:
-// the sharers then hit that XCD's L2 instead of re-pulling HBM (the GQA
-// staging re-read is the dominant prefill cost, profiles/).
-// DB=1: T14 register staging (issue tile t+1's global loads BEFORE tile
-// t's compute, write them to LDS after the barrier) — HBM latency hides
-// under the MFMAs at the cost of ~32 staging VGPRs (guide G15/T14).
-// NW: waves per block (4 -> 64 q rows, 8 -> 128 q rows; the bigger tile
-// halves K/V staging traffic per output row).
-template <int SWZ, int DB, int NW>
-__global__ __launch_bounds__(NW * 64) void prefill_attn_kernel(
-    __hip_bfloat16* __restrict__ out,        // [T, QH, D]
-    const __hip_bfloat16* __restrict__ q,    // [T, QH, D]
-    const __hip_bfloat16* __restrict__ k,    // [T, KVH, D]
-    const __hip_bfloat16* __restrict__ v,    // [T, KVH, D]
-    const int* __restrict__ block_info,      // [nblocks, 4] =
-    //   (q_start_row, q_block, kv_start_row, q_offset) — q_offset is the
-    //   position of q row 0 within the sequence (prefix caching / chunked
-    //   prefill attend over [past; new] K/V)
-    const int* __restrict__ seq_lens,        // [nblocks] KV length of the seq
-    const float scale, const int num_q_heads, const int num_kv_heads,
-    const int q_stride, const int kv_stride,
-    const int nblocks) {
+template <int SWZ>
+DEV_INLINE PrefillBlock prefill_block(const int* block_info,
+                                      const int* seq_lens, int num_q_heads,
+                                      int num_kv_heads, int nblocks) {
   const int qpg_n = num_q_heads / num_kv_heads;
-  int blk, qh;
+  int blk;
+  PrefillBlock b;
   if (SWZ && qpg_n > 1) {
     // group g = (block, kvh); its qpg_n sharers get ids c*8*qpg + q*8 + g%8
     const int lin = blockIdx.x;
@@ -95,17 +60,91 @@ __global__ __launch_bounds__(NW * 64) void prefill_attn_kernel(
       qpg_idx = idx % qpg_n;
     }
     blk = g / num_kv_heads;
-    qh = (g % num_kv_heads) * qpg_n + qpg_idx;
+    b.qh = (g % num_kv_heads) * qpg_n + qpg_idx;
   } else {
     blk = blockIdx.x / num_q_heads;
-    qh = blockIdx.x % num_q_heads;
+    b.qh = blockIdx.x % num_q_heads;
   }
-  const int kvh = qh / qpg_n;
-  const int q_start = block_info[blk * 4];
-  const int qblock = block_info[blk * 4 + 1];
-  const int kv_start = block_info[blk * 4 + 2];
-  const int q_offset = block_info[blk * 4 + 3];
-  const int seq_len = seq_lens[blk];     // total KV tokens
+  b.kvh = b.qh / qpg_n;
+  b.q_start = block_info[blk * 4];
+  b.qblock = block_info[blk * 4 + 1];
+  b.kv_start = block_info[blk * 4 + 2];
+  b.q_offset = block_info[blk * 4 + 3];
+  b.seq_len = seq_lens[blk];
+  return b;
+}
+
+// K/V tile staging, shared by both kernels.  PF_STAGING(IMG_OFF) declares
+// the staging registers and two helpers: issue_loads(kt) starts the global
+// loads of 64-key tile kt, write_tile() lands them in k_lds and in v_img at
+// the V image layout IMG_OFF(key, dim).  Each thread owns PIECES (<= 4)
+// (key, 8-dim chunk) pieces of the tile.  Uses the kernel's tid, NTHREADS,
+// PIECES, k, v, kv_start, kv_stride, kvh, seq_len, k_lds and v_img.
+// UNCONDITIONAL clamped loads: a per-piece `if (krow < seq_len)` guard
+// makes hipcc branch around each load and drain vmcnt(0) per element
+// (guide §5 trap 4c); out-of-range rows are masked in softmax anyway.
+// SCALAR staging registers: `uint4 kreg[PIECES]` arrays were demoted to
+// scratch memory by the compiler (ISA: scratch_store/load_dwordx4 in
+// the k-tile loop), silently tripling the staged tile's HBM traffic —
+// the same demotion found while building skinny_gemm.hip
+#define PF_LD(s, kt2, kr, vr)                                               \
+  do {                                                                      \
+    const int piece = tid + (s) * NTHREADS;                                 \
+    const size_t row =                                                      \
+        (size_t)(kv_start + min((kt2) * KTILE + (piece >> 4), seq_len - 1)) * \
+            kv_stride +                                                     \
+        (size_t)kvh * HEAD_DIM + (piece & 15) * 8;                          \
+    kr = *reinterpret_cast<const uint4*>(k + row);                          \
+    vr = *reinterpret_cast<const uint4*>(v + row);                          \
+  } while (0)
+#define PF_ST(s, kr, vr, IMG_OFF)                                           \
+  do {                                                                      \
+    const int piece = tid + (s) * NTHREADS;                                 \
+    const int key = piece >> 4, chunk = (piece & 15) * 8;                   \
+    *reinterpret_cast<uint4*>(&k_lds[key][chunk]) = kr;                     \
+    *reinterpret_cast<uint4*>(&v_img[IMG_OFF(key, chunk)]) = vr;            \
+  } while (0)
+#define PF_STAGING(IMG_OFF)                                                 \
+  uint4 kr0 = {}, kr1 = {}, kr2 = {}, kr3 = {};                             \
+  uint4 vr0 = {}, vr1 = {}, vr2 = {}, vr3 = {};                             \
+  auto issue_loads = [&](int kt2) {                                         \
+    PF_LD(0, kt2, kr0, vr0);                                                \
+    if (PIECES > 1) PF_LD(1, kt2, kr1, vr1);                                \
+    if (PIECES > 2) PF_LD(2, kt2, kr2, vr2);                                \
+    if (PIECES > 3) PF_LD(3, kt2, kr3, vr3);                                \
+  };                                                                        \
+  auto write_tile = [&]() {                                                 \
+    PF_ST(0, kr0, vr0, IMG_OFF);                                            \
+    if (PIECES > 1) PF_ST(1, kr1, vr1, IMG_OFF);                            \
+    if (PIECES > 2) PF_ST(2, kr2, vr2, IMG_OFF);                            \
+    if (PIECES > 3) PF_ST(3, kr3, vr3, IMG_OFF);                            \
+  }
+
+
+// SWZ=1: XCD-affine block ids (prefill_block).
+// DB=1: T14 register staging (issue tile t+1's global loads BEFORE tile
+// t's compute, write them to LDS after the barrier) — HBM latency hides
+// under the MFMAs at the cost of ~32 staging VGPRs (guide G15/T14).
+// NW: waves per block (4 -> 64 q rows, 8 -> 128 q rows; the bigger tile
+// halves K/V staging traffic per output row).
+template <int SWZ, int DB, int NW>
+__global__ __launch_bounds__(NW * 64) void prefill_attn_kernel(
+    __hip_bfloat16* __restrict__ out,        // [T, QH, D]
+    const __hip_bfloat16* __restrict__ q,    // [T, QH, D]
+    const __hip_bfloat16* __restrict__ k,    // [T, KVH, D]
+    const __hip_bfloat16* __restrict__ v,    // [T, KVH, D]
+    const int* __restrict__ block_info,      // [nblocks, 4] =
+    //   (q_start_row, q_block, kv_start_row, q_offset)
+    const int* __restrict__ seq_lens,        // [nblocks] KV length of the seq
+    const float scale, const int num_q_heads, const int num_kv_heads,
+    const int q_stride, const int kv_stride,
+    const int nblocks) {
+  const PrefillBlock pb = prefill_block<SWZ>(block_info, seq_lens,
+                                             num_q_heads, num_kv_heads,
+                                             nblocks);
+  const int qh = pb.qh, kvh = pb.kvh, q_start = pb.q_start;
+  const int qblock = pb.qblock, kv_start = pb.kv_start;
+  const int q_offset = pb.q_offset, seq_len = pb.seq_len;
 
   constexpr int QTILE = NW * 16;     // q rows per block (16 per wave)
   constexpr int NTHREADS = NW * 64;
@@ -123,7 +162,7 @@ __global__ __launch_bounds__(NW * 64) void prefill_attn_kernel(
   const int num_q_rows = seq_len - q_offset;    // rows in the q tensor
   const int q_row_in_chunk = qblock * QTILE + wave * 16 + gl;
   const int q_row = q_start + min(q_row_in_chunk, num_q_rows - 1);
-  mfma_bf8 q_frag[4];
+  bf8 q_frag[4];
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks)
     q_frag[ks] = load_bf8(q + (size_t)q_row * q_stride +
@@ -131,7 +170,7 @@ __global__ __launch_bounds__(NW * 64) void prefill_attn_kernel(
 
   // per-lane softmax state: 4 q-rows (rows 4*gslice + r of the wave tile)
   float m_run[4], l_run[4];
-  mfma_f4 acc_o[8];    // O[16 x 128]: 8 col-tiles of 16 dims
+  f32x4 acc_o[8];    // O[16 x 128]: 8 col-tiles of 16 dims
 #pragma unroll
   for (int r = 0; r < 4; ++r) { m_run[r] = NEG_INF; l_run[r] = 0.f; }
 #pragma unroll
@@ -144,47 +183,9 @@ __global__ __launch_bounds__(NW * 64) void prefill_attn_kernel(
                              seq_len - 1);
   const int nktiles = block_q_max / KTILE + 1;
 
-  // staging helpers: each thread owns 4 (key, chunk) pieces of a tile.
-  // UNCONDITIONAL clamped loads: a per-piece `if (krow < seq_len)` guard
-  // makes hipcc branch around each load and drain vmcnt(0) per element
-  // (guide §5 trap 4c); out-of-range rows are masked in softmax anyway.
   constexpr int PIECES = KTILE * (HEAD_DIM / 8) / NTHREADS;  // per thread
   static_assert(PIECES <= 4, "scalar staging sets cover 4 pieces");
-  // SCALAR staging registers: `uint4 kreg[PIECES]` arrays were demoted to
-  // scratch memory by the compiler (ISA: scratch_store/load_dwordx4 in
-  // the k-tile loop), silently tripling the staged tile's HBM traffic —
-  // the same demotion found while building skinny_gemm.hip
-  uint4 kr0 = {}, kr1 = {}, kr2 = {}, kr3 = {};
-  uint4 vr0 = {}, vr1 = {}, vr2 = {}, vr3 = {};
-#define PF_ROW(s, kt2)                                                      \
-  ((size_t)(kv_start + min((kt2) * KTILE + ((tid + (s) * NTHREADS) >> 4),  \
-                           seq_len - 1)) * kv_stride +                      \
-   (size_t)kvh * HEAD_DIM + ((tid + (s) * NTHREADS) & 15) * 8)
-#define PF_LD(s, kt2, kr, vr)                                               \
-  do {                                                                      \
-    const size_t row = PF_ROW(s, kt2);                                      \
-    kr = *reinterpret_cast<const uint4*>(k + row);                          \
-    vr = *reinterpret_cast<const uint4*>(v + row);                          \
-  } while (0)
-  auto issue_loads = [&](int kt2) {
-    PF_LD(0, kt2, kr0, vr0);
-    if (PIECES > 1) PF_LD(1, kt2, kr1, vr1);
-    if (PIECES > 2) PF_LD(2, kt2, kr2, vr2);
-    if (PIECES > 3) PF_LD(3, kt2, kr3, vr3);
-  };
-#define PF_ST(s, kr, vr)                                                    \
-  do {                                                                      \
-    const int key = (tid + (s) * NTHREADS) >> 4;                            \
-    const int chunk = ((tid + (s) * NTHREADS) & 15) * 8;                    \
-    *reinterpret_cast<uint4*>(&k_lds[key][chunk]) = kr;                     \
-    *reinterpret_cast<uint4*>(&v_img[v_img_off(key, chunk)]) = vr;          \
-  } while (0)
-  auto write_tile = [&]() {
-    PF_ST(0, kr0, vr0);
-    if (PIECES > 1) PF_ST(1, kr1, vr1);
-    if (PIECES > 2) PF_ST(2, kr2, vr2);
-    if (PIECES > 3) PF_ST(3, kr3, vr3);
-  };
+  PF_STAGING(v_img_off);
 
   if (DB) {   // prologue: tile 0 resident before the loop
     issue_loads(0);
@@ -196,7 +197,7 @@ __global__ __launch_bounds__(NW * 64) void prefill_attn_kernel(
     if (DB) {
       __syncthreads();                 // tile kt visible to every wave
       if (kt + 1 < nktiles)
-        issue_loads(kt + 1);           // in flight under the MFMAs below
+        issue_loads(kt + 1);        // in flight under the MFMAs below
     } else {
       __syncthreads();
       issue_loads(kt);
@@ -208,13 +209,13 @@ __global__ __launch_bounds__(NW * 64) void prefill_attn_kernel(
     if (compute_this) {
 
     // ---- S = Q K^T : 4 col-tiles x 4 k-steps of MFMA --------------------
-    mfma_f4 s[4];
+    f32x4 s[4];
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct) {
       s[ct] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
-        mfma_bf8 kf = lds_bf8(&k_lds[ct * 16 + gl][ks * 32 + gslice * 8]);
+        bf8 kf = load_bf8(&k_lds[ct * 16 + gl][ks * 32 + gslice * 8]);
         s[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q_frag[ks], kf, s[ct],
                                                         0, 0, 0);
       }
@@ -265,49 +266,14 @@ __global__ __launch_bounds__(NW * 64) void prefill_attn_kernel(
     // hardware-transpose reads (ds_read_b64_tr_b16) ------------------------
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      mfma_bf8 pa = lds_bf8(&p_lds[wave][gl][ks * 32 + gslice * 8]);
-      const unsigned vaddr = (unsigned)(unsigned long long)(
-          &v_img[ks * 4096 + gslice * 64 + gl * 4]);
-      unsigned long long vlo[8], vhi[8];
-      asm volatile(
-          "ds_read_b64_tr_b16 %0, %16\n\t"
-          "ds_read_b64_tr_b16 %1, %16 offset:512\n\t"
-          "ds_read_b64_tr_b16 %2, %16 offset:1024\n\t"
-          "ds_read_b64_tr_b16 %3, %16 offset:1536\n\t"
-          "ds_read_b64_tr_b16 %4, %16 offset:2048\n\t"
-          "ds_read_b64_tr_b16 %5, %16 offset:2560\n\t"
-          "ds_read_b64_tr_b16 %6, %16 offset:3072\n\t"
-          "ds_read_b64_tr_b16 %7, %16 offset:3584\n\t"
-          "ds_read_b64_tr_b16 %8, %16 offset:4096\n\t"
-          "ds_read_b64_tr_b16 %9, %16 offset:4608\n\t"
-          "ds_read_b64_tr_b16 %10, %16 offset:5120\n\t"
-          "ds_read_b64_tr_b16 %11, %16 offset:5632\n\t"
-          "ds_read_b64_tr_b16 %12, %16 offset:6144\n\t"
-          "ds_read_b64_tr_b16 %13, %16 offset:6656\n\t"
-          "ds_read_b64_tr_b16 %14, %16 offset:7168\n\t"
-          "ds_read_b64_tr_b16 %15, %16 offset:7680\n\t"
-          "s_waitcnt lgkmcnt(0)"
-          : "=&v"(vlo[0]), "=&v"(vhi[0]), "=&v"(vlo[1]), "=&v"(vhi[1]),
-            "=&v"(vlo[2]), "=&v"(vhi[2]), "=&v"(vlo[3]), "=&v"(vhi[3]),
-            "=&v"(vlo[4]), "=&v"(vhi[4]), "=&v"(vlo[5]), "=&v"(vhi[5]),
-            "=&v"(vlo[6]), "=&v"(vhi[6]), "=&v"(vlo[7]), "=&v"(vhi[7])
-          : "v"(vaddr)
-          : "memory");
-      __builtin_amdgcn_sched_barrier(0);   // rule 18: keep MFMAs below
-#pragma unroll
-      for (int dt = 0; dt < 8; ++dt) {
-        union { struct { unsigned long long lo, hi; } u; mfma_bf8 vf2; } vf;
-        vf.u.lo = vlo[dt];
-        vf.u.hi = vhi[dt];
-        acc_o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, vf.vf2,
-                                                            acc_o[dt], 0, 0, 0);
-      }
+      const bf8 pa = load_bf8(&p_lds[wave][gl][ks * 32 + gslice * 8]);
+      PV_STEP16(acc_o, pa, v_img_lane_addr(&v_img[ks * 4096], gl, gslice));
     }
     }  // compute_this
 
     if (DB && kt + 1 < nktiles) {
       __syncthreads();                 // every wave done READING tile kt
-      write_tile();                    // land tile kt+1 (write-after-barrier)
+      write_tile();        // land tile kt+1 (write-after-barrier)
     }
   }
 
@@ -347,8 +313,6 @@ DEV_INLINE int v_img32_off(int key, int dim) {
          (2 * h + ((dim >> 4) & 1)) * 64 + (j7 & 3) * 16 + (dim & 15);
 }
 
-typedef __attribute__((ext_vector_type(16))) float mfma_f16;
-
 template <int SWZ, int DB>
 __global__ __launch_bounds__(256, 2) void prefill_attn32_kernel(
     __hip_bfloat16* __restrict__ out,        // [T, QH, D]
@@ -359,35 +323,12 @@ __global__ __launch_bounds__(256, 2) void prefill_attn32_kernel(
     const int* __restrict__ seq_lens,        // [nblocks]
     const float scale, const int num_q_heads, const int num_kv_heads,
     const int q_stride, const int kv_stride, const int nblocks) {
-  const int qpg_n = num_q_heads / num_kv_heads;
-  int blk, qh;
-  if (SWZ && qpg_n > 1) {
-    const int lin = blockIdx.x;
-    const int G = nblocks * num_kv_heads;
-    const int chunk = 8 * qpg_n;
-    const int full = (G / 8) * chunk;
-    int g, qpg_idx;
-    if (lin < full) {
-      const int c = lin / chunk, r = lin % chunk;
-      qpg_idx = r >> 3;
-      g = c * 8 + (r & 7);
-    } else {
-      const int idx = lin - full;
-      g = (G / 8) * 8 + idx / qpg_n;
-      qpg_idx = idx % qpg_n;
-    }
-    blk = g / num_kv_heads;
-    qh = (g % num_kv_heads) * qpg_n + qpg_idx;
-  } else {
-    blk = blockIdx.x / num_q_heads;
-    qh = blockIdx.x % num_q_heads;
-  }
-  const int kvh = qh / qpg_n;
-  const int q_start = block_info[blk * 4];
-  const int qblock = block_info[blk * 4 + 1];
-  const int kv_start = block_info[blk * 4 + 2];
-  const int q_offset = block_info[blk * 4 + 3];
-  const int seq_len = seq_lens[blk];
+  const PrefillBlock pb = prefill_block<SWZ>(block_info, seq_lens,
+                                             num_q_heads, num_kv_heads,
+                                             nblocks);
+  const int qh = pb.qh, kvh = pb.kvh, q_start = pb.q_start;
+  const int qblock = pb.qblock, kv_start = pb.kv_start;
+  const int q_offset = pb.q_offset, seq_len = pb.seq_len;
 
   constexpr int QTILE = 128;        // 4 waves x 32 rows
   constexpr int NTHREADS = 256;
@@ -405,7 +346,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn32_kernel(
   const int num_q_rows = seq_len - q_offset;
   const int q_row_in_chunk = qblock * QTILE + wave * 32 + col;
   const int q_row = q_start + min(q_row_in_chunk, num_q_rows - 1);
-  mfma_bf8 q_frag[8];
+  bf8 q_frag[8];
 #pragma unroll
   for (int ks = 0; ks < 8; ++ks)
     q_frag[ks] = load_bf8(q + (size_t)q_row * q_stride +
@@ -413,7 +354,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn32_kernel(
 
   // softmax state: the lane's 16 rows r(i) = (i%4) + 4*half + 8*(i/4)
   float m_run[16], l_run[16];
-  mfma_f16 acc_o[4];                // O[32 x 128]: 4 col-tiles of 32 dims
+  f32x16 acc_o[4];                // O[32 x 128]: 4 col-tiles of 32 dims
 #pragma unroll
   for (int i = 0; i < 16; ++i) { m_run[i] = NEG_INF; l_run[i] = 0.f; }
 #pragma unroll
@@ -428,31 +369,11 @@ __global__ __launch_bounds__(256, 2) void prefill_attn32_kernel(
   const int nktiles = block_q_max / KTILE + 1;
 
   constexpr int PIECES = KTILE * (HEAD_DIM / 8) / NTHREADS;   // = 4
-  uint4 kr0 = {}, kr1 = {}, kr2 = {}, kr3 = {};
-  uint4 vr0 = {}, vr1 = {}, vr2 = {}, vr3 = {};
-  auto issue_loads32 = [&](int kt2) {
-    PF_LD(0, kt2, kr0, vr0);
-    PF_LD(1, kt2, kr1, vr1);
-    PF_LD(2, kt2, kr2, vr2);
-    PF_LD(3, kt2, kr3, vr3);
-  };
-#define PF_ST32(s, kr, vr)                                                  \
-  do {                                                                      \
-    const int key = (tid + (s) * NTHREADS) >> 4;                            \
-    const int chunk = ((tid + (s) * NTHREADS) & 15) * 8;                    \
-    *reinterpret_cast<uint4*>(&k_lds[key][chunk]) = kr;                     \
-    *reinterpret_cast<uint4*>(&v_img[v_img32_off(key, chunk)]) = vr;        \
-  } while (0)
-  auto write_tile32 = [&]() {
-    PF_ST32(0, kr0, vr0);
-    PF_ST32(1, kr1, vr1);
-    PF_ST32(2, kr2, vr2);
-    PF_ST32(3, kr3, vr3);
-  };
+  PF_STAGING(v_img32_off);
 
   if (DB) {
-    issue_loads32(0);
-    write_tile32();
+    issue_loads(0);
+    write_tile();
   }
 
   for (int kt = 0; kt < nktiles; ++kt) {
@@ -460,11 +381,11 @@ __global__ __launch_bounds__(256, 2) void prefill_attn32_kernel(
     if (DB) {
       __syncthreads();
       if (kt + 1 < nktiles)
-        issue_loads32(kt + 1);
+        issue_loads(kt + 1);
     } else {
       __syncthreads();
-      issue_loads32(kt);
-      write_tile32();
+      issue_loads(kt);
+      write_tile();
       __syncthreads();
     }
 
@@ -472,14 +393,14 @@ __global__ __launch_bounds__(256, 2) void prefill_attn32_kernel(
     if (compute_this) {
 
     // ---- S = Q K^T : 2 col-tiles (32 keys) x 8 k-steps ------------------
-    mfma_f16 s[2];
+    f32x16 s[2];
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) s[ct][i] = 0.f;
 #pragma unroll
       for (int ks = 0; ks < 8; ++ks) {
-        mfma_bf8 kf = lds_bf8(
+        bf8 kf = load_bf8(
             &k_lds[ct * 32 + col][ks * 16 + half * 8]);
         s[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
             q_frag[ks], kf, s[ct], 0, 0, 0);
@@ -512,7 +433,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn32_kernel(
     // ---- O += P V : 4 col-tiles x 4 key-steps ---------------------------
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      mfma_bf8 pa = lds_bf8(&p_lds[wave][col][ks * 16 + half * 8]);
+      bf8 pa = load_bf8(&p_lds[wave][col][ks * 16 + half * 8]);
       const unsigned vbase = (unsigned)(unsigned long long)(
           &v_img[ks * 2048 + (lane >> 4) * 64 + (lane & 15) * 4]);
 #pragma unroll
@@ -525,7 +446,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn32_kernel(
             : "=&v"(vlo), "=&v"(vhi)
             : "v"(vbase), "i"(dt * 1024), "i"(dt * 1024 + 512)
             : "memory");
-        union { struct { unsigned long long lo, hi; } u; mfma_bf8 vf; } vv;
+        union { struct { unsigned long long lo, hi; } u; bf8 vf; } vv;
         vv.u.lo = vlo;
         vv.u.hi = vhi;
         acc_o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
@@ -536,7 +457,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn32_kernel(
 
     if (DB && kt + 1 < nktiles) {
       __syncthreads();
-      write_tile32();
+      write_tile();
     }
   }
 
@@ -557,6 +478,35 @@ __global__ __launch_bounds__(256, 2) void prefill_attn32_kernel(
   }
 }
 
+#undef PF_LD
+#undef PF_ST
+#undef PF_STAGING
+
+typedef void (*PrefillKernel)(__hip_bfloat16*, const __hip_bfloat16*,
+                              const __hip_bfloat16*, const __hip_bfloat16*,
+                              const int*, const int*, float, int, int, int,
+                              int, int);
+
+// swz bit 0: XCD-affine GQA swizzle; bit 1: T14 double-buffer staging;
+// bit 2: 8-wave blocks (host must build block_info with qtile=128);
+// bit 3: 32x32x16 MFMA kernel (4 waves, qtile=128; bit 2 is ignored)
+PrefillKernel prefill_kernel(int swz) {
+  switch (swz & 8 ? swz & 11 : swz & 7) {
+    case 0: return prefill_attn_kernel<0, 0, 4>;
+    case 1: return prefill_attn_kernel<1, 0, 4>;
+    case 2: return prefill_attn_kernel<0, 1, 4>;
+    case 3: return prefill_attn_kernel<1, 1, 4>;
+    case 4: return prefill_attn_kernel<0, 0, 8>;
+    case 5: return prefill_attn_kernel<1, 0, 8>;
+    case 6: return prefill_attn_kernel<0, 1, 8>;
+    case 7: return prefill_attn_kernel<1, 1, 8>;
+    case 8: return prefill_attn32_kernel<0, 0>;
+    case 9: return prefill_attn32_kernel<1, 0>;
+    case 10: return prefill_attn32_kernel<0, 1>;
+    default: return prefill_attn32_kernel<1, 1>;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -567,46 +517,13 @@ void launch_prefill_attention(void* out, const void* q, const void* k,
                               int num_q_heads, int num_kv_heads, int swz,
                               int q_stride, int kv_stride,
                               hipStream_t stream) {
-  dim3 grid(nblocks * num_q_heads);
-  // swz bit 0: XCD-affine GQA swizzle; bit 1: T14 double-buffer staging;
-  // bit 2: 8-wave blocks (host must build block_info with qtile=128);
-  // bit 3: 32x32x16 MFMA kernel (4 waves, qtile=128)
-  if (swz & 8) {
-#define PF32_LAUNCH(S, D)                                                   \
-    hipLaunchKernelGGL((prefill_attn32_kernel<S, D>), grid, dim3(256), 0,   \
-                       stream,                                              \
-                       (__hip_bfloat16*)out, (const __hip_bfloat16*)q,      \
-                       (const __hip_bfloat16*)k, (const __hip_bfloat16*)v,  \
-                       (const int*)block_info, (const int*)seq_lens, scale, \
-                       num_q_heads, num_kv_heads, q_stride, kv_stride,      \
-                       nblocks)
-    switch (swz & 3) {
-      case 0: PF32_LAUNCH(0, 0); break;
-      case 1: PF32_LAUNCH(1, 0); break;
-      case 2: PF32_LAUNCH(0, 1); break;
-      case 3: PF32_LAUNCH(1, 1); break;
-    }
-#undef PF32_LAUNCH
-    return;
-  }
-#define PF_LAUNCH(S, D, NW)                                                 \
-  hipLaunchKernelGGL((prefill_attn_kernel<S, D, NW>), grid, dim3(NW * 64),  \
-                     0, stream,                                             \
-                     (__hip_bfloat16*)out, (const __hip_bfloat16*)q,        \
-                     (const __hip_bfloat16*)k, (const __hip_bfloat16*)v,    \
-                     (const int*)block_info, (const int*)seq_lens, scale,   \
-                     num_q_heads, num_kv_heads, q_stride, kv_stride, nblocks)
-  switch (swz & 7) {
-    case 0: PF_LAUNCH(0, 0, 4); break;
-    case 1: PF_LAUNCH(1, 0, 4); break;
-    case 2: PF_LAUNCH(0, 1, 4); break;
-    case 3: PF_LAUNCH(1, 1, 4); break;
-    case 4: PF_LAUNCH(0, 0, 8); break;
-    case 5: PF_LAUNCH(1, 0, 8); break;
-    case 6: PF_LAUNCH(0, 1, 8); break;
-    case 7: PF_LAUNCH(1, 1, 8); break;
-  }
-#undef PF_LAUNCH
+  const dim3 grid(nblocks * num_q_heads);
+  const dim3 block((swz & 12) == 4 ? 512 : 256);   // only bit 2 alone: 8 waves
+  hipLaunchKernelGGL(prefill_kernel(swz), grid, block, 0, stream,
+                     (__hip_bfloat16*)out, (const __hip_bfloat16*)q,
+                     (const __hip_bfloat16*)k, (const __hip_bfloat16*)v,
+                     (const int*)block_info, (const int*)seq_lens, scale,
+                     num_q_heads, num_kv_heads, q_stride, kv_stride, nblocks);
 }
 
 }  // extern "C"

@@ -195,7 +195,7 @@ torch::Tensor decode_attention(torch::Tensor q, torch::Tensor key_cache,
                                torch::Tensor value_cache,
                                torch::Tensor block_tables,
                                torch::Tensor context_lens, double scale,
-                               int64_t num_splits, int64_t wide) {
+                               int64_t num_splits, int64_t variant) {
   // q may be a slice of the fused QKV projection: 3-D bf16 with
   // contiguous (head, dim) rows and an arbitrary token stride
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16 &&
@@ -237,7 +237,7 @@ torch::Tensor decode_attention(torch::Tensor q, torch::Tensor key_cache,
                           key_cache.data_ptr(), value_cache.data_ptr(),
                           block_tables.data_ptr(), context_lens.data_ptr(),
                           (float)scale, num_seqs, num_q_heads, num_kv_heads,
-                          page_size, max_pages, (int)num_splits, (int)wide,
+                          page_size, max_pages, (int)num_splits, (int)variant,
                           (int)q.stride(0), current_stream());
   return out;
 }
