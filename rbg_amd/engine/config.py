@@ -12,6 +12,18 @@ from __future__ import annotations
 from dataclasses import dataclass, field
 
 
+KV_CACHE_DTYPES = ("bf16", "fp8_e4m3")
+KV_SCALE_LOG2_MIN, KV_SCALE_LOG2_MAX = -16, 16
+
+
+def kv_element_size(kv_cache_dtype: str) -> int:
+    """Bytes per cached K/V element."""
+    if kv_cache_dtype not in KV_CACHE_DTYPES:
+        raise ValueError("unknown kv_cache_dtype %r (one of %s)" % (
+            kv_cache_dtype, ", ".join(KV_CACHE_DTYPES)))
+    return 2 if kv_cache_dtype == "bf16" else 1
+
+
 @dataclass
 class ModelConfig:
     name: str = "llama-3-8b"
@@ -36,8 +48,9 @@ class ModelConfig:
     def kv_size(self) -> int:
         return self.num_kv_heads * self.head_dim
 
-    def kv_bytes_per_token(self) -> int:
-        return 2 * self.num_layers * self.num_kv_heads * self.head_dim * 2
+    def kv_bytes_per_token(self, kv_cache_dtype: str = "bf16") -> int:
+        return (2 * self.num_layers * self.num_kv_heads * self.head_dim *
+                kv_element_size(kv_cache_dtype))
 
     @staticmethod
     def preset(name: str) -> "ModelConfig":
@@ -98,3 +111,33 @@ class EngineConfig:
     enable_prefix_cache: bool = True   # full-page KV reuse (Mooncake analog)
     enforce_eager: bool = False        # False: capture decode in hipGraphs
     seed: int = 0
+    # KV pool element type (docs/FEATURES.md "FP8 KV cache"): "fp8_e4m3"
+    # caches sat_rne_e4m3fn(x * 2^-e) and reads e4m3 * 2^e, with one
+    # power-of-two exponent each for K and V
+    kv_cache_dtype: str = "bf16"
+    kv_k_scale_log2: int = 0
+    kv_v_scale_log2: int = 0
+
+    def __post_init__(self) -> None:
+        kv_element_size(self.kv_cache_dtype)       # raises on an unknown name
+        for name in ("kv_k_scale_log2", "kv_v_scale_log2"):
+            e = getattr(self, name)
+            if (isinstance(e, bool) or not isinstance(e, int) or
+                    not KV_SCALE_LOG2_MIN <= e <= KV_SCALE_LOG2_MAX):
+                raise ValueError("%s must be an integer in [%d, %d], got %r"
+                                 % (name, KV_SCALE_LOG2_MIN,
+                                    KV_SCALE_LOG2_MAX, e))
+        if self.kv_cache_dtype != "bf16" and (
+                self.page_size != 16 or self.model.head_dim != 128):
+            raise ValueError("kv_cache_dtype %r needs page_size 16 and "
+                             "head_dim 128" % self.kv_cache_dtype)
+
+    @property
+    def kv_fp8(self) -> bool:
+        return self.kv_cache_dtype == "fp8_e4m3"
+
+    def kv_signature(self) -> dict:
+        """What two pools must agree on before KV bytes move between them."""
+        return {"kv_cache_dtype": self.kv_cache_dtype,
+                "kv_k_scale_log2": self.kv_k_scale_log2,
+                "kv_v_scale_log2": self.kv_v_scale_log2}

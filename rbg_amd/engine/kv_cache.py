@@ -1,7 +1,8 @@
 """Paged KV cache — the HBM3E pool behind prefill/decode attention.
 
 One contiguous allocation per engine holds every layer's K and V pages
-(layout [layers, 2, pages, kv_heads, page_size, head_dim] bf16) so the pool
+(layout [layers, 2, pages, kv_heads, page_size, head_dim], bf16 or e4m3
+bytes per EngineConfig.kv_cache_dtype) so the pool
 is sized ONCE against the GPU's 288 GB and the per-layer kernel views are
 zero-copy slices.  Pages are the transfer unit for P->D KV migration
 (parallel/kv_transfer.py): a sequence's pages can be copied peer-to-peer
@@ -17,7 +18,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from .config import EngineConfig
+from .config import EngineConfig, kv_element_size
 
 
 class OutOfPages(RuntimeError):
@@ -38,6 +39,14 @@ class PagedKVCache:
         self.num_pages = num_pages
         kvh = m.num_kv_heads // max(1, cfg.tp_size)   # TP shards the heads
         shape = (layers, 2, num_pages, kvh, cfg.page_size, m.head_dim)
+        # element type of the pool (docs/FEATURES.md "FP8 KV cache"); the
+        # exponents ride with the pool so every reader and writer of it
+        # agrees on what a cached byte means
+        self.kv_cache_dtype = cfg.kv_cache_dtype
+        self.fp8 = cfg.kv_fp8
+        self.k_scale_log2 = cfg.kv_k_scale_log2 if self.fp8 else 0
+        self.v_scale_log2 = cfg.kv_v_scale_log2 if self.fp8 else 0
+        dtype = torch.float8_e4m3fn if self.fp8 else torch.bfloat16
         self.ipc_exportable = False
         if device.type == "cuda":
             # hipMalloc base allocation (not the caching allocator) so the
@@ -45,8 +54,12 @@ class PagedKVCache:
             # migrated pages straight over xGMI (parallel/kv_peer.py)
             from .. import ops
             if ops.HAVE_HIP:
-                self.kv = ops._require_hip().ipc_alloc_bf16(list(shape))
-                self.kv.zero_()
+                if self.fp8:
+                    self.kv = ops._require_hip().ipc_alloc(list(shape), dtype)
+                    self.kv.view(torch.uint8).zero_()
+                else:
+                    self.kv = ops._require_hip().ipc_alloc_bf16(list(shape))
+                    self.kv.zero_()
                 self.ipc_exportable = True
                 # incarnation token: a RECREATED engine's pool can receive
                 # identical hipIpc handle bytes (deterministic allocator),
@@ -56,10 +69,9 @@ class PagedKVCache:
                 import uuid as _uuid
                 self.ipc_uid = _uuid.uuid4().hex
             else:
-                self.kv = torch.zeros(shape, dtype=torch.bfloat16,
-                                      device=device)
+                self.kv = torch.zeros(shape, dtype=dtype, device=device)
         else:
-            self.kv = torch.zeros(shape, dtype=torch.bfloat16, device=device)
+            self.kv = torch.zeros(shape, dtype=dtype, device=device)
         # page 0 is reserved scratch: hipGraph decode padding rows write
         # their (dead) KV slot there (model_runner._decode_graph)
         self._free: List[int] = list(range(num_pages - 1, 0, -1))
@@ -74,7 +86,8 @@ class PagedKVCache:
         m = cfg.model
         kvh = m.num_kv_heads // max(1, cfg.tp_size)
         page_bytes = ((num_layers or m.num_layers) * 2 * kvh *
-                      cfg.page_size * m.head_dim * 2)
+                      cfg.page_size * m.head_dim *
+                      kv_element_size(cfg.kv_cache_dtype))
         if device.type == "cuda" and torch.cuda.is_available():
             free, _total = torch.cuda.mem_get_info(device)
             budget = int(free * cfg.gpu_memory_utilization)
@@ -118,6 +131,12 @@ class PagedKVCache:
 
     def tokens_capacity(self) -> int:
         return self.num_pages * self.page_size
+
+    def signature(self) -> Dict[str, object]:
+        """Element type and exponents: pools exchanging pages must agree."""
+        return {"kv_cache_dtype": self.kv_cache_dtype,
+                "kv_k_scale_log2": self.k_scale_log2,
+                "kv_v_scale_log2": self.v_scale_log2}
 
 
 class BlockTable:

@@ -40,9 +40,10 @@ class ModelRunner:
             cfg.page_size
         self._graphs: Dict[int, Tuple] = {}
         self._graph_pool = None
-        log.info("model %s on %s: %d KV pages (%.1f GB pool)",
+        log.info("model %s on %s: %d KV pages (%.1f GB pool, %s)",
                  cfg.model.name, self.device, self.cache.num_pages,
-                 self.cache.kv.numel() * 2 / 1e9)
+                 self.cache.kv.numel() * self.cache.kv.element_size() / 1e9,
+                 cfg.kv_cache_dtype)
 
     # ------------------------------------------------------------------
 
@@ -63,7 +64,12 @@ class ModelRunner:
         cu_k = [0]
         completing: List[Sequence] = []
         last_idx: List[int] = []
-        any_past = any(seq.num_prefilled > 0 for seq in seqs)
+        # an fp8 pool always attends through the gather path, so a key made
+        # in this very step is seen as dq(q8(.)) like every other key and
+        # the logits depend on the token history alone (prefix hit or miss,
+        # chunked or whole prefill)
+        any_past = (any(seq.num_prefilled > 0 for seq in seqs) or
+                    self.cache.fp8)
         for seq in seqs:
             start = seq.num_prefilled
             end = start + (seq.chunk_len or

@@ -56,6 +56,9 @@ def _engine_cfg(ctx: WorkerContext) -> EngineConfig:
         enable_prefix_cache=bool(args.get("enable_prefix_cache", True)),
         max_prefill_tokens=int(args.get("max_prefill_tokens", 8192)),
         enforce_eager=bool(args.get("enforce_eager", device != "cuda")),
+        kv_cache_dtype=str(args.get("kv_cache_dtype", "bf16")),
+        kv_k_scale_log2=int(args.get("kv_k_scale_log2", 0)),
+        kv_v_scale_log2=int(args.get("kv_v_scale_log2", 0)),
     )
 
 
@@ -246,11 +249,11 @@ class ServeWorker:
     def _send_pages(self, pages: List[int], dst_rank: int) -> None:
         import torch.distributed as dist
 
-        from ..parallel.comm import to_wire
+        from ..parallel.comm import pool_bytes, to_wire
         cache = self.engine.runner.cache
         with self._xfer_lock:
             idx = torch.tensor(pages, dtype=torch.int64, device=cache.kv.device)
-            buf = cache.kv.index_select(2, idx).contiguous()
+            buf = pool_bytes(cache.kv).index_select(2, idx).contiguous()
             if buf.device != self._xfer_buf_device():
                 buf = buf.to(self._xfer_buf_device())
             dist.send(to_wire(buf), dst_rank)
@@ -258,7 +261,7 @@ class ServeWorker:
     def _recv_pages(self, pages: List[int], src_rank: int) -> None:
         import torch.distributed as dist
 
-        from ..parallel.comm import from_wire, wire_dtype
+        from ..parallel.comm import from_wire, pool_bytes, wire_dtype
         cache = self.engine.runner.cache
         with self._xfer_lock:
             m = cache.kv.shape
@@ -267,9 +270,10 @@ class ServeWorker:
                               dtype=wire_dtype(cache.kv.dtype, dev),
                               device=dev)
             dist.recv(buf, src_rank)
-            buf = from_wire(buf, cache.kv.dtype)
+            pool = pool_bytes(cache.kv)
+            buf = from_wire(buf, pool.dtype)
             idx = torch.tensor(pages, dtype=torch.int64, device=cache.kv.device)
-            cache.kv.index_copy_(2, idx, buf.to(cache.kv.device))
+            pool.index_copy_(2, idx, buf.to(cache.kv.device))
 
     def _peer_rank(self, peer_instance: str) -> int:
         """My point-to-point counterpart in `peer_instance`: same position
@@ -394,6 +398,9 @@ class ServeWorker:
 
         def stats():
             out = self.engine.stats.snapshot()
+            out["kv_cache"] = dict(
+                self.engine.runner.cache.signature(),
+                num_pages=self.engine.runner.cache.num_pages)
             if self._xfer_stats["pushes"]:
                 xs = dict(self._xfer_stats)
                 xs["gb_per_s"] = round(
@@ -536,7 +543,9 @@ class ServeWorker:
         first_token = seq.output_tokens[0]
         meta = dict(tokens=tokens, first_token=first_token,
                     num_pages=len(pages), max_new_tokens=max_new_tokens,
-                    arrival_time=seq.arrival_time, **seq.sampling.wire())
+                    arrival_time=seq.arrival_time,
+                    kv=self.engine.runner.cache.signature(),
+                    **seq.sampling.wire())
         peer_ok = self._peer_possible()
         if self.gcomm is not None:
             client = RpcClient("127.0.0.1",
@@ -656,7 +665,14 @@ class ServeWorker:
                         arrival_time: float = 0.0,
                         peer_ok: bool = False, top_p: float = 1.0,
                         top_k: int = 0, min_p: float = 0.0,
-                        seed: Optional[int] = None) -> Dict[str, Any]:
+                        seed: Optional[int] = None,
+                        kv: Optional[Dict[str, Any]] = None
+                        ) -> Dict[str, Any]:
+        # the sender's pool must hold what mine holds (element type and both
+        # exponents): refuse before a page is allocated or a byte moves
+        from ..parallel.comm import check_kv_signature
+        check_kv_signature(self.engine.runner.cache.signature(), kv,
+                           "import_seq")
         sampling = {"temperature": temperature, "top_p": top_p,
                     "top_k": top_k, "min_p": min_p, "seed": seed}
         if peer_ok and self._peer_possible():

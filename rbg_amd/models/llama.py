@@ -213,11 +213,29 @@ class LlamaAttention(nn.Module):
         key_cache = kv.key_cache(self.layer_idx)
         value_cache = kv.value_cache(self.layer_idx)
         # fused RoPE + paged KV write (q,k rotated in place)
-        ops.rope_store_kv(q, k, v, key_cache, value_cache, cos_sin,
-                          batch.positions, batch.slot_mapping)
+        fp8 = kv.fp8
+        if fp8:
+            ops.rope_store_kv(q, k, v, key_cache, value_cache, cos_sin,
+                              batch.positions, batch.slot_mapping,
+                              kv.k_scale_log2, kv.v_scale_log2)
+        else:
+            ops.rope_store_kv(q, k, v, key_cache, value_cache, cos_sin,
+                              batch.positions, batch.slot_mapping)
         q3 = q.view(T, self.heads, self.head_dim)
         if batch.mode == "prefill":
-            if batch.kv_gather_slots is not None:
+            if fp8:
+                # every key, this step's included, is read back dequantised
+                if batch.kv_gather_slots is None:
+                    raise RuntimeError("an fp8 KV pool prefills through the "
+                                       "gather path: kv_gather_slots unset")
+                k_full = ops.kv_gather_dequant(
+                    key_cache, batch.kv_gather_slots, kv.k_scale_log2)
+                v_full = ops.kv_gather_dequant(
+                    value_cache, batch.kv_gather_slots, kv.v_scale_log2)
+                o = ops.prefill_attention(q3, k_full, v_full,
+                                          batch.cu_seqlens, self.scale,
+                                          batch.cu_seqlens_k)
+            elif batch.kv_gather_slots is not None:
                 ps = key_cache.shape[2]
                 slots = batch.kv_gather_slots.long()
                 pages, offs = slots // ps, slots % ps
@@ -231,6 +249,13 @@ class LlamaAttention(nn.Module):
                     q3, k.view(T, self.kv_heads, self.head_dim),
                     v.view(T, self.kv_heads, self.head_dim),
                     batch.cu_seqlens, self.scale)
+        elif fp8:
+            o = ops.decode_attention(q3, key_cache, value_cache,
+                                     batch.block_tables, batch.context_lens,
+                                     self.scale,
+                                     num_splits=batch.decode_num_splits,
+                                     k_scale_log2=kv.k_scale_log2,
+                                     v_scale_log2=kv.v_scale_log2)
         else:
             o = ops.decode_attention(q3, key_cache, value_cache,
                                      batch.block_tables, batch.context_lens,

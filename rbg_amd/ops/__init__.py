@@ -109,14 +109,57 @@ def silu_mul(x: torch.Tensor) -> torch.Tensor:
     return reference.silu_mul(x)
 
 
+FP8 = torch.float8_e4m3fn
+KV_CACHE_DTYPES = reference.KV_CACHE_DTYPES
+KV_SCALE_LOG2_RANGE = reference.KV_SCALE_LOG2_RANGE
+check_kv_scale_log2 = reference.check_kv_scale_log2
+
+
+def _is_fp8_pair(key_cache, value_cache) -> bool:
+    """True for an e4m3 cache pair (docs/FEATURES.md "FP8 KV cache"); a pair
+    of differing dtypes raises before anything is launched."""
+    if key_cache.dtype != value_cache.dtype:
+        raise ValueError("key_cache is %s but value_cache is %s" % (
+            key_cache.dtype, value_cache.dtype))
+    return key_cache.dtype == FP8
+
+
 def rope_store_kv(q, k, v, key_cache, value_cache, cos_sin, positions,
-                  slot_mapping) -> None:
+                  slot_mapping, k_scale_log2: int = 0,
+                  v_scale_log2: int = 0) -> None:
+    """RoPE on q, k in place, then the paged KV write.  An e4m3 cache
+    receives sat_rne_e4m3fn(x * 2^-e) of the bf16 value a bf16 cache would
+    have received; the exponents are ignored for a bf16 cache."""
+    if _is_fp8_pair(key_cache, value_cache):
+        check_kv_scale_log2(k_scale_log2, "kv_k_scale_log2")
+        check_kv_scale_log2(v_scale_log2, "kv_v_scale_log2")
+        if _on_gpu(q):
+            _require_hip().rope_store_kv_fp8(
+                q, k, v, key_cache, value_cache, cos_sin, positions,
+                slot_mapping, k_scale_log2, v_scale_log2)
+            return
+        reference.rope_store_kv(q, k, v, key_cache, value_cache, cos_sin,
+                                positions, slot_mapping, k_scale_log2,
+                                v_scale_log2)
+        return
     if _on_gpu(q):
         _require_hip().rope_store_kv(q, k, v, key_cache, value_cache,
                                      cos_sin, positions, slot_mapping)
         return
     reference.rope_store_kv(q, k, v, key_cache, value_cache, cos_sin,
                             positions, slot_mapping)
+
+
+def kv_gather_dequant(cache, slots, scale_log2: int = 0) -> torch.Tensor:
+    """Rows of an e4m3 cache [pages, KVH, page, D] by slot, dequantised:
+    bf16 [Tkv, KVH, D] = e4m3(byte) * 2^scale_log2 (exact)."""
+    if cache.dtype != FP8:
+        raise ValueError("kv_gather_dequant needs a float8_e4m3fn cache, "
+                         "got %s" % cache.dtype)
+    check_kv_scale_log2(scale_log2, "scale_log2")
+    if _on_gpu(cache):
+        return _require_hip().kv_gather_dequant(cache, slots, scale_log2)
+    return reference.kv_gather_dequant(cache, slots, scale_log2)
 
 
 def pick_decode_splits(num_seqs: int, num_kv_heads: int,
@@ -148,7 +191,31 @@ PREFILL_SWZ = int(os.environ.get("RBG_PREFILL_SWZ", "6"))  # 8-wave + K/V double
 
 def decode_attention(q, key_cache, value_cache, block_tables, context_lens,
                      scale: float, num_splits: int = 0,
-                     variant: int = -1) -> torch.Tensor:
+                     variant: int = -1, k_scale_log2: int = 0,
+                     v_scale_log2: int = 0) -> torch.Tensor:
+    if _is_fp8_pair(key_cache, value_cache):
+        # one kernel reads an e4m3 cache: the page-pair MFMA one (variant 4)
+        if variant not in (-1, 4):
+            raise ValueError("an fp8 KV cache has no decode variant %d: only "
+                             "variant 4 reads e4m3" % variant)
+        check_kv_scale_log2(k_scale_log2, "kv_k_scale_log2")
+        check_kv_scale_log2(v_scale_log2, "kv_v_scale_log2")
+        if key_cache.shape[2] != 16 or key_cache.shape[3] != 128:
+            raise ValueError("fp8 decode needs page size 16 and head_dim 128, "
+                             "got %d and %d" % (key_cache.shape[2],
+                                                key_cache.shape[3]))
+        if _on_gpu(q):
+            if num_splits <= 0:
+                max_ctx = (int(context_lens.max().item())
+                           if context_lens.numel() else 1)
+                num_splits = pick_decode_splits(q.shape[0],
+                                                key_cache.shape[1], max_ctx, 4)
+            return _require_hip().decode_attention_fp8(
+                q, key_cache, value_cache, block_tables, context_lens, scale,
+                num_splits, k_scale_log2, v_scale_log2)
+        return reference.decode_attention(
+            q, key_cache, value_cache, block_tables, context_lens, scale,
+            k_scale_log2, v_scale_log2)
     if _on_gpu(q):
         if num_splits <= 0:
             max_ctx = int(context_lens.max().item()) if context_lens.numel() else 1

@@ -17,6 +17,8 @@
 //        consumer wave.
 // Variants 4-6 need page_size == 16; with any other page size, and for
 // out-of-range variants, the launcher falls back to variant 1.
+// An FP8 (e4m3) cache has one kernel of its own, decode_attn_mfma_fp8_kernel:
+// variant 4 with a dequantising stage (launch_decode_attention_fp8).
 //
 // Capability analog: the decode-side paged attention of the engines the
 // reference orchestrates (SURVEY §2.3 decode engine row).
@@ -688,6 +690,151 @@ __global__ __launch_bounds__(128, 4) void decode_attn_pc_kernel(
                          gslice);
 }
 
+// ---------------------------------------------------------------------------
+// FP8 (OCP e4m3fn) cache decode: variant 4 with a dequantising stage.  A
+// page slice [16 tokens][128 d] is 2 KB of bytes, so the lane's share of a
+// page pair is 64 B = 4 x 16 B pieces (named scalars Q0..Q3, as above).  The
+// bytes become bf16 on their way into the K panel / V image; the conversion
+// is exact, since e4m3's four significant bits and its exponent range fit a
+// bf16.  LDS then
+// holds exactly what variant 4 would have staged from the dequantised cache
+// with both exponents 0; the power-of-two scales are applied where they are
+// exact and free: 2^ek folded into the score scale, 2^ev into the epilogue.
+// Everything after the stage (S MFMAs, softmax, PV, epilogue) is variant 4's
+// code, in variant 4's order.
+
+DEV_INLINE uint2 fp8x4_to_bf16x4(unsigned w) {
+  // v_cvt_scalef32_pk_bf16_fp8 with scale 1: two e4m3 bytes -> two packed
+  // bf16 in ONE instruction (half the VALU work of v_cvt_pk_f32_fp8 plus a
+  // v_perm of the high halves, which measured slower: docs/STATUS.md)
+  typedef __attribute__((ext_vector_type(2))) __bf16 bf2;
+  union { bf2 v; unsigned u; } lo, hi;
+  lo.v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false);
+  hi.v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true);
+  uint2 r;
+  r.x = lo.u;
+  r.y = hi.u;
+  return r;
+}
+
+// 16 e4m3 bytes -> 16 bf16 as two 16-byte pieces (elements 0-7, 8-15)
+DEV_INLINE void fp8x16_to_bf16(const uint4& b, uint4& lo, uint4& hi) {
+  const uint2 a0 = fp8x4_to_bf16x4(b.x), a1 = fp8x4_to_bf16x4(b.y);
+  const uint2 a2 = fp8x4_to_bf16x4(b.z), a3 = fp8x4_to_bf16x4(b.w);
+  lo = make_uint4(a0.x, a0.y, a1.x, a1.y);
+  hi = make_uint4(a2.x, a2.y, a3.x, a3.y);
+}
+
+#define DQ_REGS(R) uint4 R##0, R##1, R##2, R##3
+#define DQ_ISSUE(cache, R, pg)                                              \
+  do {                                                                      \
+    const int p_ = btab[min((pg) + myloc, pg_last)];                        \
+    const uint8_t* src_ = (cache) + schunk +                                \
+        (((size_t)p_ * num_kv_heads + kvh) * 16 + (srow & 15)) * HEAD_DIM;  \
+    R##0 = *reinterpret_cast<const uint4*>(src_);                           \
+    R##1 = *reinterpret_cast<const uint4*>(src_ + 16);                      \
+    R##2 = *reinterpret_cast<const uint4*>(src_ + 32);                      \
+    R##3 = *reinterpret_cast<const uint4*>(src_ + 48);                      \
+  } while (0)
+#define DQ_WRITE1(r, AT, c)                                                 \
+  do {                                                                      \
+    uint4 lo_, hi_;                                                         \
+    fp8x16_to_bf16(r, lo_, hi_);                                            \
+    *reinterpret_cast<uint4*>(AT(c)) = lo_;                                 \
+    *reinterpret_cast<uint4*>(AT((c) + 8)) = hi_;                           \
+  } while (0)
+#define DQ_WRITE(R, AT)                                                     \
+  do {                                                                      \
+    DQ_WRITE1(R##0, AT, 0);                                                 \
+    DQ_WRITE1(R##1, AT, 16);                                                \
+    DQ_WRITE1(R##2, AT, 32);                                                \
+    DQ_WRITE1(R##3, AT, 48);                                                \
+  } while (0)
+
+template <int QPG>
+__global__ __launch_bounds__(128, 3) void decode_attn_mfma_fp8_kernel(
+    float* __restrict__ partial_o,        // [splits, seqs, QH, D]
+    float* __restrict__ partial_ml,       // [splits, seqs, QH, 2]
+    __hip_bfloat16* __restrict__ out,     // [seqs, QH, D] (splits==1 path)
+    const __hip_bfloat16* __restrict__ q, // [seqs, QH, D]
+    const uint8_t* __restrict__ key_cache,   // [pages, KVH, 16, D] e4m3
+    const uint8_t* __restrict__ val_cache,
+    const int* __restrict__ block_tables, // [seqs, max_pages]
+    const int* __restrict__ context_lens, // [seqs]
+    const float scale,                    // softmax scale * 2^ek
+    const float v_scale,                  // 2^ev
+    const int num_kv_heads, const int max_pages,
+    const int num_splits, const int num_seqs, const int q_stride) {
+  const int kvh = blockIdx.x;
+  const int wave = threadIdx.x >> 6;
+  const int seq = blockIdx.y * 2 + wave;
+  const int split = blockIdx.z;
+  const int lane = threadIdx.x & 63;
+  const int gl = lane & 15;
+  const int gslice = lane >> 4;
+
+  // per-wave LDS, K panel and V image sharing one buffer (see variant 4)
+  __shared__ __hip_bfloat16 kv_all[2][32 * DM_KP];
+  __shared__ __hip_bfloat16 p_lds_all[2][16 * DM_PP];
+  __hip_bfloat16* k_lds = kv_all[wave];
+  __hip_bfloat16* v_img = kv_all[wave];
+  __hip_bfloat16* p_lds = p_lds_all[wave];
+  if (seq >= num_seqs) return;
+  const SplitRange sr = split_range(context_lens[seq], split, num_splits);
+
+  bf8 qa[4];
+  load_q_frags<QPG>(qa, q + (size_t)seq * q_stride, kvh, gl, gslice);
+
+  const int* btab = block_tables + (size_t)seq * max_pages;
+  // the lane's key row of the pair and its 64-element (= 64-byte) half row
+  const int srow = lane >> 1, schunk = (lane & 1) * 64, myloc = srow >> 4;
+  const int pg_last = max(sr.pg_end - 1, 0);
+  DQ_REGS(ka);
+
+  float m[4], l[4];
+  f32x4 acc_o[8];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) { m[r] = NEG_INF; l[r] = 0.f; }
+#pragma unroll
+  for (int dt = 0; dt < 8; ++dt) acc_o[dt] = {0.f, 0.f, 0.f, 0.f};
+
+  DQ_ISSUE(key_cache, ka, sr.pg_begin);
+
+  for (int pg = sr.pg_begin; pg < sr.pg_end; pg += 2) {
+    DQ_WRITE(ka, DM_K_AT);
+    DQ_REGS(va);
+    DQ_ISSUE(val_cache, va, pg);          // V hides under S
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+
+    f32x4 sA, sB;
+    score_pair(sA, sB, qa, k_lds, gl, gslice);
+    pair_softmax(sA, sB, scale, pg, sr, m, l, acc_o, p_lds, gl, gslice);
+    // V overwrites the K panel: same-wave DS ordering protects the S
+    // fragment reads issued above
+    DQ_WRITE(va, DM_V_AT);
+    DQ_ISSUE(key_cache, ka, pg + 2);      // next pair's K hides under PV
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+
+    const bf8 pa = load_p_frag(p_lds, gl, gslice);
+    const unsigned vaddr = v_img_lane_addr(v_img, gl, gslice);
+    PV_STEP16(acc_o, pa, vaddr);
+  }
+
+  // 2^ev: exact, and the split combine is linear in O
+#pragma unroll
+  for (int dt = 0; dt < 8; ++dt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc_o[dt][r] *= v_scale;
+
+  store_pair_output<QPG>(partial_o, partial_ml, out, acc_o, m, l, seq,
+                         num_seqs, split, num_splits, kvh, num_kv_heads, gl,
+                         gslice);
+}
+
+#undef DQ_REGS
+#undef DQ_ISSUE
+#undef DQ_WRITE1
+#undef DQ_WRITE
 #undef DM_REGS
 #undef DM_ISSUE
 #undef DM_K_AT
@@ -777,6 +924,43 @@ void launch_decode_attention(void* out, void* partial_o, void* partial_ml,
                      scale, num_kv_heads, mfma ? max_pages : page_size,
                      mfma ? num_splits : max_pages,
                      mfma ? num_seqs : num_splits, q_stride);
+  if (num_splits > 1) {
+    dim3 cgrid(num_seqs, num_q_heads), cblock(HEAD_DIM);
+    hipLaunchKernelGGL(decode_combine_kernel, cgrid, cblock, 0, stream,
+                       (__hip_bfloat16*)out, (const float*)partial_o,
+                       (const float*)partial_ml, num_splits, num_q_heads);
+  }
+}
+
+// e4m3 caches with 16-token pages (validated host-side).  k_scale is the
+// softmax scale times 2^ek, v_scale is 2^ev.
+void launch_decode_attention_fp8(void* out, void* partial_o, void* partial_ml,
+                                 const void* q, const void* key_cache,
+                                 const void* val_cache,
+                                 const void* block_tables,
+                                 const void* context_lens, float k_scale,
+                                 float v_scale, int num_seqs, int num_q_heads,
+                                 int num_kv_heads, int max_pages,
+                                 int num_splits, int q_stride,
+                                 hipStream_t stream) {
+  typedef void (*Fp8Kernel)(float*, float*, __hip_bfloat16*,
+                            const __hip_bfloat16*, const uint8_t*,
+                            const uint8_t*, const int*, const int*, float,
+                            float, int, int, int, int, int);
+  const int qpg = num_q_heads / num_kv_heads;
+  const Fp8Kernel kernel = qpg == 1   ? decode_attn_mfma_fp8_kernel<1>
+                           : qpg == 2 ? decode_attn_mfma_fp8_kernel<2>
+                           : qpg == 4 ? decode_attn_mfma_fp8_kernel<4>
+                           : qpg == 8 ? decode_attn_mfma_fp8_kernel<8>
+                                      : nullptr;
+  if (kernel == nullptr) return;   // validated host-side
+  const dim3 grid(num_kv_heads, (num_seqs + 1) / 2, num_splits);
+  hipLaunchKernelGGL(kernel, grid, dim3(128), 0, stream, (float*)partial_o,
+                     (float*)partial_ml, (__hip_bfloat16*)out,
+                     (const __hip_bfloat16*)q, (const uint8_t*)key_cache,
+                     (const uint8_t*)val_cache, (const int*)block_tables,
+                     (const int*)context_lens, k_scale, v_scale, num_kv_heads,
+                     max_pages, num_splits, num_seqs, q_stride);
   if (num_splits > 1) {
     dim3 cgrid(num_seqs, num_q_heads), cblock(HEAD_DIM);
     hipLaunchKernelGGL(decode_combine_kernel, cgrid, cblock, 0, stream,

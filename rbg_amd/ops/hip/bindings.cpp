@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -37,6 +38,15 @@ void launch_xgmi_allreduce(void*, const void*, void**, void**, int, int,
 void launch_sample(void*, void*, const void*, const void*, const void*,
                    const void*, const void*, const void*, const void*, int,
                    int, hipStream_t);
+void launch_rope_store_kv_fp8(void*, void*, const void*, void*, void*,
+                              const void*, const void*, const void*, int, int,
+                              int, int, int, int, float, float, hipStream_t);
+void launch_kv_gather_dequant(void*, const void*, const void*, long, int, int,
+                              int, float, hipStream_t);
+void launch_decode_attention_fp8(void*, void*, void*, const void*, const void*,
+                                 const void*, const void*, const void*, float,
+                                 float, int, int, int, int, int, int,
+                                 hipStream_t);
 long xgmi_allreduce_signal_bytes();
 long xgmi_allreduce_error_offset();
 long xgmi_allreduce_counter_offset();
@@ -242,6 +252,160 @@ torch::Tensor decode_attention(torch::Tensor q, torch::Tensor key_cache,
   return out;
 }
 
+// ---- FP8 (OCP e4m3fn) paged KV cache --------------------------------------
+// Separate entry points: the bf16 ones above keep rejecting every non-bf16
+// cache.  Scales are powers of two given as integer exponents.
+
+float check_scale_log2(int64_t e, const char* name) {
+  TORCH_CHECK(e >= -16 && e <= 16, name, " must be in [-16, 16], got ", e);
+  return std::ldexp(1.0f, (int)e);
+}
+
+void check_fp8_cache(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.scalar_type() == torch::kFloat8_e4m3fn, name,
+              " must be float8_e4m3fn");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.dim() == 4, name,
+              " must be [pages, KVH, page_size, head_dim]");
+  const int64_t page_size = t.size(2);
+  TORCH_CHECK(page_size > 0 && (page_size & (page_size - 1)) == 0,
+              "page_size must be a power of two");
+  TORCH_CHECK(t.size(1) > 0, "cache needs at least one KV head");
+  TORCH_CHECK(t.size(3) == 128, "fp8 cache head_dim must be 128");
+  TORCH_CHECK(t.numel() / 128 <= INT32_MAX, "cache has too many slots");
+}
+
+void check_fp8_caches(const torch::Tensor& key_cache,
+                      const torch::Tensor& value_cache) {
+  TORCH_CHECK(key_cache.scalar_type() == value_cache.scalar_type(),
+              "key_cache/value_cache dtype mismatch");
+  check_fp8_cache(key_cache, "key_cache");
+  check_fp8_cache(value_cache, "value_cache");
+  TORCH_CHECK(value_cache.sizes() == key_cache.sizes(),
+              "key_cache/value_cache shape mismatch");
+  TORCH_CHECK(value_cache.device() == key_cache.device(),
+              "key_cache/value_cache device mismatch");
+}
+
+void rope_store_kv_fp8(torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                       torch::Tensor key_cache, torch::Tensor value_cache,
+                       torch::Tensor cos_sin, torch::Tensor positions,
+                       torch::Tensor slot_mapping, int64_t k_scale_log2,
+                       int64_t v_scale_log2) {
+  check_bf16_rowslice(q, "q");
+  check_bf16_rowslice(k, "k");
+  check_bf16_rowslice(v, "v");
+  TORCH_CHECK(k.stride(0) == v.stride(0), "k/v stride mismatch");
+  check_fp8_caches(key_cache, value_cache);
+  const float k_inv = check_scale_log2(-k_scale_log2, "kv_k_scale_log2");
+  const float v_inv = check_scale_log2(-v_scale_log2, "kv_v_scale_log2");
+  check_i32_gpu(positions, "positions");
+  check_i32_gpu(slot_mapping, "slot_mapping");
+  TORCH_CHECK(cos_sin.scalar_type() == torch::kFloat32 && cos_sin.is_cuda() &&
+              cos_sin.is_contiguous() && cos_sin.dim() == 2,
+              "cos_sin must be a contiguous 2-D fp32 GPU tensor");
+  const int tokens = q.size(0);
+  const int num_kv_heads = key_cache.size(1);
+  const int page_size = key_cache.size(2);
+  TORCH_CHECK(cos_sin.size(1) == 128,
+              "cos_sin row width must equal the cache head_dim");
+  TORCH_CHECK(k.size(0) == tokens && v.size(0) == tokens &&
+              positions.numel() == tokens && slot_mapping.numel() == tokens,
+              "q/k/v/positions/slot_mapping token counts differ");
+  const int64_t q_width = q.numel() / std::max(tokens, 1);
+  const int64_t k_width = k.numel() / std::max(tokens, 1);
+  const int64_t v_width = v.numel() / std::max(tokens, 1);
+  TORCH_CHECK(k_width == (int64_t)num_kv_heads * 128 && v_width == k_width,
+              "k/v rows must be cache KVH * head_dim wide");
+  TORCH_CHECK(q_width % 128 == 0,
+              "q row width must be a multiple of the cache head_dim");
+  // V rows are read as 16-byte vectors
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(v.data_ptr()) % 16 == 0 &&
+              v.stride(0) % 8 == 0, "v rows must be 16-byte aligned");
+  if (tokens == 0) return;
+  launch_rope_store_kv_fp8(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                           key_cache.data_ptr(), value_cache.data_ptr(),
+                           cos_sin.data_ptr(), positions.data_ptr(),
+                           slot_mapping.data_ptr(), tokens,
+                           (int)(q_width / 128), num_kv_heads, page_size,
+                           (int)q.stride(0), (int)k.stride(0), k_inv, v_inv,
+                           current_stream());
+}
+
+torch::Tensor kv_gather_dequant(torch::Tensor cache, torch::Tensor slots,
+                                int64_t scale_log2) {
+  check_fp8_cache(cache, "cache");
+  check_i32_gpu(slots, "slots");
+  TORCH_CHECK(slots.dim() == 1 && slots.device() == cache.device(),
+              "slots must be 1-D on the cache's device");
+  const float scale = check_scale_log2(scale_log2, "scale_log2");
+  const int64_t tokens = slots.numel();
+  const int num_kv_heads = cache.size(1);
+  auto out = torch::empty({tokens, (int64_t)num_kv_heads, (int64_t)128},
+                          cache.options().dtype(torch::kBFloat16));
+  if (tokens == 0) return out;
+  launch_kv_gather_dequant(out.data_ptr(), cache.data_ptr(), slots.data_ptr(),
+                           (long)tokens, (int)(cache.numel() / 128 /
+                                               num_kv_heads),
+                           num_kv_heads, (int)cache.size(2), scale,
+                           current_stream());
+  return out;
+}
+
+torch::Tensor decode_attention_fp8(torch::Tensor q, torch::Tensor key_cache,
+                                   torch::Tensor value_cache,
+                                   torch::Tensor block_tables,
+                                   torch::Tensor context_lens, double scale,
+                                   int64_t num_splits, int64_t k_scale_log2,
+                                   int64_t v_scale_log2) {
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16 &&
+              q.dim() == 3 && q.stride(2) == 1 &&
+              q.stride(1) == q.size(2), "q must be [T, QH, D] row-sliced");
+  const int num_seqs = q.size(0);
+  const int num_q_heads = q.size(1);
+  TORCH_CHECK(q.size(2) == 128, "head_dim must be 128");
+  check_fp8_caches(key_cache, value_cache);
+  TORCH_CHECK(key_cache.size(2) == 16,
+              "fp8 decode needs a page size of 16");
+  const float k_scale = check_scale_log2(k_scale_log2, "kv_k_scale_log2");
+  const float v_scale = check_scale_log2(v_scale_log2, "kv_v_scale_log2");
+  const int num_kv_heads = key_cache.size(1);
+  TORCH_CHECK(num_q_heads % num_kv_heads == 0,
+              "q heads must be a multiple of the cache KV heads");
+  const int qpg = num_q_heads / num_kv_heads;
+  TORCH_CHECK(qpg == 1 || qpg == 2 || qpg == 4 || qpg == 8,
+              "GQA group must be 1/2/4/8");
+  check_i32_gpu(block_tables, "block_tables");
+  check_i32_gpu(context_lens, "context_lens");
+  TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(0) == num_seqs,
+              "block_tables must be [num_seqs, max_pages]");
+  TORCH_CHECK(context_lens.dim() == 1 && context_lens.size(0) == num_seqs,
+              "context_lens must be [num_seqs]");
+  TORCH_CHECK(num_splits >= 1, "num_splits must be >= 1");
+  const int max_pages = block_tables.size(1);
+  auto out = torch::empty({num_seqs, num_q_heads, 128}, q.options());
+  if (num_seqs == 0) return out;
+  torch::Tensor partial_o, partial_ml;
+  void *po = nullptr, *pml = nullptr;
+  if (num_splits > 1) {
+    auto opts = q.options().dtype(torch::kFloat32);
+    partial_o = torch::empty({num_splits, num_seqs, num_q_heads, 128}, opts);
+    partial_ml = torch::empty({num_splits, num_seqs, num_q_heads, 2}, opts);
+    po = partial_o.data_ptr();
+    pml = partial_ml.data_ptr();
+  }
+  // 2^ek folds into the score scale: a power of two, so the product is exact
+  launch_decode_attention_fp8(out.data_ptr(), po, pml, q.data_ptr(),
+                              key_cache.data_ptr(), value_cache.data_ptr(),
+                              block_tables.data_ptr(),
+                              context_lens.data_ptr(), (float)scale * k_scale,
+                              v_scale, num_seqs, num_q_heads, num_kv_heads,
+                              max_pages, (int)num_splits, (int)q.stride(0),
+                              current_stream());
+  return out;
+}
+
 torch::Tensor prefill_attention(torch::Tensor q, torch::Tensor k,
                                 torch::Tensor v, torch::Tensor block_info,
                                 torch::Tensor seq_lens, double scale,
@@ -405,6 +569,22 @@ torch::Tensor ipc_alloc_bf16(std::vector<int64_t> sizes) {
       ptr, sizes, [](void* p) { (void)hipFree(p); }, opts);
 }
 
+// The same allocation for any element type (the fp8 KV pool).
+torch::Tensor ipc_alloc(std::vector<int64_t> sizes, torch::ScalarType dtype) {
+  int64_t numel = 1;
+  for (auto s : sizes) numel *= s;
+  const int64_t bytes = numel * (int64_t)c10::elementSize(dtype);
+  void* ptr = nullptr;
+  hipError_t err = hipMalloc(&ptr, bytes);
+  TORCH_CHECK(err == hipSuccess, "hipMalloc(", bytes,
+              " B) failed: ", hipGetErrorString(err));
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  auto opts = torch::TensorOptions().dtype(dtype).device(torch::kCUDA, dev);
+  return torch::from_blob(
+      ptr, sizes, [](void* p) { (void)hipFree(p); }, opts);
+}
+
 py::bytes kv_ipc_export(torch::Tensor pool) {
   TORCH_CHECK(pool.is_cuda(), "pool must be on GPU");
   hipIpcMemHandle_t handle;
@@ -438,9 +618,15 @@ void kv_ipc_close(int64_t ptr) {
 void kv_peer_copy(int64_t dst_base, torch::Tensor src_kv,
                   torch::Tensor src_pages, torch::Tensor dst_pages,
                   int64_t dst_num_pages) {
-  // src_kv: [L, 2, Ps, kvh, ps, hd] bf16 contiguous; dst pool has the SAME
-  // per-page layout but its own page count (dst_num_pages)
-  check_bf16_contig(src_kv, "src_kv");
+  // src_kv: [L, 2, Ps, kvh, ps, hd] bf16 or e4m3, contiguous; dst pool has
+  // the SAME element type and per-page layout but its own page count
+  // (dst_num_pages).  The copy moves bytes: chunks are counted in 16-byte
+  // vectors.
+  TORCH_CHECK(src_kv.is_cuda(), "src_kv must be on GPU");
+  TORCH_CHECK(src_kv.scalar_type() == torch::kBFloat16 ||
+                  src_kv.scalar_type() == torch::kFloat8_e4m3fn,
+              "src_kv must be bf16 or float8_e4m3fn");
+  TORCH_CHECK(src_kv.is_contiguous(), "src_kv must be contiguous");
   TORCH_CHECK(src_kv.dim() == 6 && src_kv.size(1) == 2, "kv must be 6-D");
   TORCH_CHECK(src_pages.is_cuda() && dst_pages.is_cuda() &&
                   src_pages.scalar_type() == torch::kInt32 &&
@@ -451,9 +637,10 @@ void kv_peer_copy(int64_t dst_base, torch::Tensor src_kv,
   if (n_pages == 0) return;
   const int layers = src_kv.size(0);
   const long Ps = src_kv.size(2);
-  const long chunk_elems = src_kv.size(3) * src_kv.size(4) * src_kv.size(5);
-  TORCH_CHECK(chunk_elems % 8 == 0, "chunk must be 16B-aligned");
-  const long chunk_vec = chunk_elems / 8;  // uint4 = 8 bf16
+  const long chunk_bytes = src_kv.size(3) * src_kv.size(4) * src_kv.size(5) *
+                           (long)src_kv.element_size();
+  TORCH_CHECK(chunk_bytes % 16 == 0, "chunk must be 16B-aligned");
+  const long chunk_vec = chunk_bytes / 16;  // uint4 vectors
   launch_kv_peer_copy(reinterpret_cast<void*>(dst_base), src_kv.data_ptr(),
                       src_pages.data_ptr(), dst_pages.data_ptr(), n_pages,
                       2 * layers, (int)chunk_vec, chunk_vec,
@@ -533,6 +720,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("silu_mul", &silu_mul, "silu(gate)*up");
   m.def("rope_store_kv", &rope_store_kv, "RoPE + paged KV write");
   m.def("decode_attention", &decode_attention, "paged flash-decode");
+  m.def("rope_store_kv_fp8", &rope_store_kv_fp8,
+        "RoPE + quantising (e4m3) paged KV write");
+  m.def("kv_gather_dequant", &kv_gather_dequant,
+        "gather e4m3 cache rows by slot -> bf16 [Tkv, KVH, D]");
+  m.def("decode_attention_fp8", &decode_attention_fp8,
+        "paged flash-decode over an e4m3 cache (page-pair MFMA)");
   m.def("prefill_attention", &prefill_attention, "varlen causal flash prefill");
   m.def("mfma_probe", &mfma_probe, "MFMA layout probe");
   m.def("mfma_probe32", &mfma_probe32, "32x32x16 MFMA layout probe");
@@ -545,6 +738,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // GIL there freezes heartbeats until the controller kills the process
   m.def("ipc_alloc_bf16", &ipc_alloc_bf16,
         "hipMalloc-backed bf16 tensor (IPC-exportable base allocation)",
+        py::call_guard<py::gil_scoped_release>());
+  m.def("ipc_alloc", &ipc_alloc,
+        "hipMalloc-backed tensor of any dtype (IPC-exportable allocation)",
         py::call_guard<py::gil_scoped_release>());
   m.def("kv_ipc_export", &kv_ipc_export, "hipIpcGetMemHandle of a KV pool");
   m.def("kv_ipc_open", &kv_ipc_open,

@@ -59,12 +59,53 @@ def apply_rope(x: torch.Tensor, positions: torch.Tensor,
     return out.to(x.dtype)
 
 
+# ---------------------------------------------------------------------------
+# FP8 (OCP e4m3fn) KV cache (docs/FEATURES.md "FP8 KV cache")
+# ---------------------------------------------------------------------------
+
+KV_CACHE_DTYPES = {"bf16": torch.bfloat16, "fp8_e4m3": torch.float8_e4m3fn}
+KV_SCALE_LOG2_RANGE = (-16, 16)
+E4M3_MAX = 448.0
+
+
+def check_kv_scale_log2(e, name: str = "scale_log2") -> int:
+    lo, hi = KV_SCALE_LOG2_RANGE
+    if isinstance(e, bool) or not isinstance(e, int) or not lo <= e <= hi:
+        raise ValueError("%s must be an integer in [%d, %d], got %r" % (
+            name, lo, hi, e))
+    return e
+
+
+def quantize_e4m3(x: torch.Tensor, scale_log2: int = 0) -> torch.Tensor:
+    """q8(x) = sat_rne_e4m3fn(x * 2^-e): round to nearest even, finite
+    overflow and +-inf saturate to +-448, NaN stays NaN.  The clamp comes
+    first because torch's own conversion turns overflow into NaN."""
+    y = x.float() * (2.0 ** -scale_log2)
+    return y.clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn)
+
+
+def dequantize_e4m3(b: torch.Tensor, scale_log2: int = 0,
+                    dtype=torch.bfloat16) -> torch.Tensor:
+    """dq(b) = e4m3(b) * 2^e, exact in bf16 (four significant bits)."""
+    return (b.float() * (2.0 ** scale_log2)).to(dtype)
+
+
+def kv_gather_dequant(cache: torch.Tensor, slots: torch.Tensor,
+                      scale_log2: int = 0) -> torch.Tensor:
+    page_size = cache.shape[2]
+    sl = slots.long()
+    rows = cache.view(torch.uint8)[sl // page_size, :, sl % page_size]
+    return dequantize_e4m3(rows.view(torch.float8_e4m3fn), scale_log2)
+
+
 def rope_store_kv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                   key_cache: torch.Tensor, value_cache: torch.Tensor,
                   cos_sin: torch.Tensor, positions: torch.Tensor,
-                  slot_mapping: torch.Tensor) -> None:
+                  slot_mapping: torch.Tensor, k_scale_log2: int = 0,
+                  v_scale_log2: int = 0) -> None:
     """Mutates q,k in place (rotated) and scatters k,v into the paged caches.
-    Cache layout: [pages, kv_heads, page_size, head_dim]."""
+    Cache layout: [pages, kv_heads, page_size, head_dim].  An e4m3 cache
+    receives quantize_e4m3 of the bf16 rows a bf16 cache would receive."""
     T = q.shape[0]
     head_dim = key_cache.shape[3]
     kvh = key_cache.shape[1]
@@ -79,15 +120,29 @@ def rope_store_kv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     valid = slots >= 0
     pages = torch.div(slots[valid], page_size, rounding_mode="floor")
     offs = slots[valid] % page_size
+    if key_cache.dtype == torch.float8_e4m3fn:
+        # index_put_ has no float8 kernel: move the bytes
+        key_cache.view(torch.uint8)[pages, :, offs] = quantize_e4m3(
+            k3[valid], k_scale_log2).view(torch.uint8)
+        value_cache.view(torch.uint8)[pages, :, offs] = quantize_e4m3(
+            v3[valid], v_scale_log2).view(torch.uint8)
+        return
     key_cache[pages, :, offs] = k3[valid]
     value_cache[pages, :, offs] = v3[valid]
 
 
 def decode_attention(q: torch.Tensor, key_cache: torch.Tensor,
                      value_cache: torch.Tensor, block_tables: torch.Tensor,
-                     context_lens: torch.Tensor, scale: float) -> torch.Tensor:
-    """q [S, QH, D] one token per sequence; paged KV."""
+                     context_lens: torch.Tensor, scale: float,
+                     k_scale_log2: int = 0,
+                     v_scale_log2: int = 0) -> torch.Tensor:
+    """q [S, QH, D] one token per sequence; paged KV.  An e4m3 cache is read
+    as e4m3(byte) * 2^e."""
     S, QH, D = q.shape
+    fp8 = key_cache.dtype == torch.float8_e4m3fn
+    if fp8:      # index the bytes: advanced indexing has no float8 kernel
+        key_cache = key_cache.view(torch.uint8)
+        value_cache = value_cache.view(torch.uint8)
     kvh = key_cache.shape[1]
     page_size = key_cache.shape[2]
     qpg = QH // kvh
@@ -98,6 +153,11 @@ def decode_attention(q: torch.Tensor, key_cache: torch.Tensor,
         pages = block_tables[s, :npages].long()
         k = key_cache[pages].permute(1, 0, 2, 3).reshape(kvh, -1, D)[:, :ctx]
         v = value_cache[pages].permute(1, 0, 2, 3).reshape(kvh, -1, D)[:, :ctx]
+        if fp8:
+            k = dequantize_e4m3(k.contiguous().view(torch.float8_e4m3fn),
+                                k_scale_log2, torch.float32)
+            v = dequantize_e4m3(v.contiguous().view(torch.float8_e4m3fn),
+                                v_scale_log2, torch.float32)
         qs = q[s].float().view(kvh, qpg, D)
         attn = torch.einsum("hgd,hkd->hgk", qs, k.float()) * scale
         p = torch.softmax(attn, dim=-1)

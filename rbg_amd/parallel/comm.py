@@ -67,18 +67,50 @@ def init_from_env(backend: Optional[str] = None,
 # gloo has no bf16 point-to-point support; every CPU-path send of bf16
 # tensors bit-reinterprets to int16 (exact) and the receiver views back.
 # Shared by PPContext hops and the KV-migration fallback so the two paths
-# can never disagree about the wire dtype.
+# can never disagree about the wire dtype.  An e4m3 KV pool travels as uint8
+# on every backend (neither gloo nor RCCL moves float8, and the pool is
+# bytes anyway).
+
+FP8 = torch.float8_e4m3fn
+
 
 def to_wire(t: torch.Tensor) -> torch.Tensor:
+    if t.dtype == FP8:
+        return t.view(torch.uint8)
     if t.device.type == "cpu" and t.dtype == torch.bfloat16:
         return t.view(torch.int16)
     return t
 
 
 def wire_dtype(dtype: torch.dtype, device: torch.device) -> torch.dtype:
+    if dtype == FP8:
+        return torch.uint8
     if device.type == "cpu" and dtype == torch.bfloat16:
         return torch.int16
     return dtype
+
+
+def pool_bytes(kv: torch.Tensor) -> torch.Tensor:
+    """The pool as a tensor the index kernels accept: an e4m3 pool as its
+    uint8 view (index_select / index_copy_ have no float8 kernels)."""
+    return kv.view(torch.uint8) if kv.dtype == FP8 else kv
+
+
+_BF16_SIGNATURE = {"kv_cache_dtype": "bf16", "kv_k_scale_log2": 0,
+                   "kv_v_scale_log2": 0}
+
+
+def check_kv_signature(mine, theirs, what: str = "KV transfer") -> None:
+    """Raise before any byte moves between pools that disagree on the element
+    type or on an exponent.  A peer that sends no signature predates the fp8
+    cache and holds bf16."""
+    theirs = dict(_BF16_SIGNATURE, **(theirs or {}))
+    mine = dict(_BF16_SIGNATURE, **(mine or {}))
+    bad = [k for k in _BF16_SIGNATURE if mine[k] != theirs[k]]
+    if bad:
+        raise ValueError("%s between mismatched KV pools: %s" % (
+            what, ", ".join("%s %r here vs %r on the peer" % (
+                k, mine[k], theirs[k]) for k in bad)))
 
 
 def from_wire(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:

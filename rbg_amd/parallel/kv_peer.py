@@ -55,6 +55,7 @@ def export_meta(cache: PagedKVCache) -> Dict[str, Any]:
         "uid": getattr(cache, "ipc_uid", ""),
         "num_pages": int(cache.kv.shape[2]),
         "shape": list(cache.kv.shape),
+        **cache.signature(),
     }
 
 
@@ -66,6 +67,7 @@ def export_meta_local(cache: PagedKVCache) -> Dict[str, Any]:
         "local_ptr": int(cache.kv.data_ptr()),
         "num_pages": int(cache.kv.shape[2]),
         "shape": list(cache.kv.shape),
+        **cache.signature(),
     }
 
 
@@ -186,6 +188,9 @@ class PeerKVPusher:
         The copy runs on this pusher's dedicated stream so it overlaps any
         compute the caller's engine keeps issuing on the default stream."""
         assert len(src_pages) == len(dst_pages)
+        # element type and exponents first: the copy moves raw bytes
+        from .comm import check_kv_signature
+        check_kv_signature(cache.signature(), dst_meta, "peer push")
         uid = str(dst_meta.get("uid", dst_meta.get("local_ptr", "")))
         with self._lock:
             if uid in self._bad:
@@ -194,7 +199,8 @@ class PeerKVPusher:
         assert list(shape)[3:] == list(dst_meta["shape"])[3:], \
             "page layout mismatch between src and dst pools"
         dst_base = self._map(dst_meta)
-        chunk_bytes = shape[3] * shape[4] * shape[5] * 2
+        chunk_bytes = (shape[3] * shape[4] * shape[5] *
+                       cache.kv.element_size())
         nbytes = len(src_pages) * 2 * shape[0] * chunk_bytes
         ev = torch.cuda.Event()
         stream = self._stream_for(uid)

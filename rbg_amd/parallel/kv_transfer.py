@@ -84,13 +84,19 @@ class TransferEngine:
                             if self.backend == "nccl" else "cpu")
 
     def send_pages(self, cache: PagedKVCache, pages: List[int],
-                   dst_rank: int) -> None:
-        from .comm import to_wire
+                   dst_rank: int, peer_signature=None) -> None:
+        """peer_signature: the receiving pool's PagedKVCache.signature()
+        where the caller knows it (the import handshake); a mismatch raises
+        before anything is sent."""
+        from .comm import check_kv_signature, pool_bytes, to_wire
+        if peer_signature is not None:
+            check_kv_signature(cache.signature(), peer_signature,
+                               "send_pages")
         self.connect()
         with self._lock:
             idx = torch.tensor(pages, dtype=torch.int64,
                                device=cache.kv.device)
-            buf = cache.kv.index_select(2, idx).contiguous()
+            buf = pool_bytes(cache.kv).index_select(2, idx).contiguous()
             if self.backend == "gloo" and buf.is_cuda:
                 buf = buf.cpu()
             buf = to_wire(buf)
@@ -103,8 +109,12 @@ class TransferEngine:
                 dist.send(buf, dst_rank)
 
     def recv_pages(self, cache: PagedKVCache, pages: List[int],
-                   src_rank: int) -> None:
-        from .comm import from_wire, wire_dtype
+                   src_rank: int, peer_signature=None) -> None:
+        from .comm import (check_kv_signature, from_wire, pool_bytes,
+                           wire_dtype)
+        if peer_signature is not None:
+            check_kv_signature(cache.signature(), peer_signature,
+                               "recv_pages")
         self.connect()
         with self._lock:
             m = cache.kv.shape
@@ -119,7 +129,8 @@ class TransferEngine:
                 self._stream.synchronize()
             else:
                 dist.recv(buf, src_rank)
-            buf = from_wire(buf, cache.kv.dtype)
+            pool = pool_bytes(cache.kv)
+            buf = from_wire(buf, pool.dtype)
             idx = torch.tensor(pages, dtype=torch.int64,
                                device=cache.kv.device)
-            cache.kv.index_copy_(2, idx, buf.to(cache.kv.device))
+            pool.index_copy_(2, idx, buf.to(cache.kv.device))

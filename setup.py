@@ -25,6 +25,7 @@ HIP_SOURCES = [
     "mfma_probe.hip",
     "rmsnorm.hip",
     "rope_kv.hip",
+    "kv_fp8.hip",
     "silu_mul.hip",
     "skinny_gemm.hip",
     "sampling.hip",
