@@ -83,10 +83,21 @@ class _Migrator:
                                         dst_pages)
             pending.wait()
         else:
+            # the same refusals as the kernel path, then a byte copy (an
+            # e4m3 pool has no index kernels of its own: pool_bytes)
+            from ..parallel.comm import check_kv_signature, pool_bytes
+            from ..parallel.kv_peer import check_push_args
+            check_kv_signature(src_cache.signature(), dst_cache.signature(),
+                               "local push")
+            check_push_args(list(src_cache.kv.shape), src_pages,
+                            {"shape": list(dst_cache.kv.shape),
+                             "num_pages": int(dst_cache.kv.shape[2])},
+                            dst_pages)
             src_idx = torch.tensor(src_pages, dtype=torch.int64)
             dst_idx = torch.tensor(dst_pages, dtype=torch.int64)
-            dst_cache.kv.index_copy_(
-                2, dst_idx, src_cache.kv.index_select(2, src_idx))
+            pool_bytes(dst_cache.kv).index_copy_(
+                2, dst_idx,
+                pool_bytes(src_cache.kv).index_select(2, src_idx))
 
     def push_remote(self, src_cache, peer_meta: Dict[str, Any],
                     src_pages: List[int], dst_pages: List[int],
@@ -120,9 +131,35 @@ def _verify() -> bool:
     return bool(os.environ.get("RBG_PD_VERIFY"))
 
 
-def _page_checksum(cache, pages: List[int]) -> float:
-    idx = torch.tensor(pages, dtype=torch.int64, device=cache.kv.device)
-    return float(cache.kv.index_select(2, idx).double().sum().item())
+_DIGEST_MUL = 0x9E3779B97F4A7C15         # odd: a bijection mod 2^64
+_DIGEST_MASK = (1 << 64) - 1
+
+
+def _page_checksum(cache, pages: List[int]) -> int:
+    """Exact, order-sensitive digest of the selected pages' bytes, as an
+    unsigned 64-bit Python int (compared with ==).
+
+    Per list position i the page's [layers * 2, words] int16 words (uint8
+    for an e4m3 pool) are summed with the odd weight 2 * (c * words + w) + 1
+    of their (chunk c = layer * 2 + k|v, offset w) place, in wrap-around
+    int64; the per-page sums are then chained, d = d * M + s_i + i + 1
+    (mod 2^64, M odd).  Moving data between layers, between K and V, between
+    offsets inside a page or between list positions changes a weight that
+    multiplies it; the plain sum this replaces was blind to all four.  One
+    page at a time, so the temporary is one page of int64."""
+    kv = cache.kv
+    raw = kv.view(torch.uint8) if kv.element_size() == 1 \
+        else kv.view(torch.int16)
+    chunks = raw.shape[0] * raw.shape[1]
+    words = raw.shape[3] * raw.shape[4] * raw.shape[5]
+    weight = (torch.arange(chunks * words, dtype=torch.int64,
+                           device=kv.device) * 2 + 1).view(chunks, words)
+    digest = 0
+    for i, pg in enumerate(pages):
+        page = raw[:, :, int(pg)].reshape(chunks, words).to(torch.int64)
+        s = int((page * weight).sum().item())          # wraps mod 2^64
+        digest = (digest * _DIGEST_MUL + s + i + 1) & _DIGEST_MASK
+    return digest
 
 
 def _prefill_batch(engine: LLMEngine, prompts: List[List[int]],
@@ -217,8 +254,7 @@ def run_pd(args, rank: int, world: int, device: str) -> Optional[dict]:
                         src_ck = _page_checksum(
                             prefill_engine.runner.cache, pages)
                         dst_ck = _page_checksum(alloc, dst)
-                        assert abs(src_ck - dst_ck) <= 1e-6 * max(
-                            1.0, abs(src_ck)), (src_ck, dst_ck)
+                        assert src_ck == dst_ck, (src_ck, dst_ck)
                     _enqueue_imported(decode_engine, s.prompt_tokens,
                                       s.output_tokens[0], dst, max_new)
                     prefill_engine.runner.cache.free(pages)
@@ -258,12 +294,13 @@ def run_pd(args, rank: int, world: int, device: str) -> Optional[dict]:
                            checks, pushed)]
                 dist.send_object_list(commit, dst=r)
                 if not pushed:
-                    from ..parallel.comm import to_wire
+                    from ..parallel.comm import pool_bytes, to_wire
                     for (_s, pages), _lst in zip(done, dst_lists):
                         idx = torch.tensor(
                             pages, dtype=torch.int64,
                             device=prefill_engine.runner.cache.kv.device)
-                        buf = prefill_engine.runner.cache.kv.index_select(
+                        buf = pool_bytes(
+                            prefill_engine.runner.cache.kv).index_select(
                             2, idx).contiguous().cpu()
                         dist.send(to_wire(buf), r)
                 now = time.monotonic()
@@ -288,7 +325,8 @@ def run_pd(args, rank: int, world: int, device: str) -> Optional[dict]:
             # CPU path, or the sender's cross-device hipIpc push was
             # refused: page data arrives over the gloo wire AFTER the
             # commit message, one set per sequence
-            from ..parallel.comm import from_wire, wire_dtype
+            from ..parallel.comm import from_wire, pool_bytes, wire_dtype
+            pool = pool_bytes(alloc.kv)
             m = alloc.kv.shape
             for _tokens, _ft, pages in entries:
                 buf = torch.empty(
@@ -298,16 +336,16 @@ def run_pd(args, rank: int, world: int, device: str) -> Optional[dict]:
                 dist.recv(buf, 0)
                 idx = torch.tensor(pages, dtype=torch.int64,
                                    device=alloc.kv.device)
-                alloc.kv.index_copy_(2, idx,
-                                     from_wire(buf, alloc.kv.dtype).to(
-                                         alloc.kv.device))
+                pool.index_copy_(2, idx,
+                                 from_wire(buf, pool.dtype).to(
+                                     alloc.kv.device))
         if checks is not None:
             # byte-exact transfer proof (RBG_PD_VERIFY=1): the imported
-            # pages must checksum identically to the sender's parked pages
+            # pages must digest identically to the sender's parked pages,
+            # in the order the sender listed them
             for (_t, _f, pages), src_ck in zip(entries, checks):
                 dst_ck = _page_checksum(alloc, pages)
-                assert abs(src_ck - dst_ck) <= 1e-6 * max(
-                    1.0, abs(src_ck)), (src_ck, dst_ck)
+                assert src_ck == dst_ck, (src_ck, dst_ck)
         for tokens, first_token, pages in entries:
             _enqueue_imported(decode_engine, tokens, first_token, pages,
                               max_new)

@@ -633,6 +633,11 @@ void kv_peer_copy(int64_t dst_base, torch::Tensor src_kv,
                   dst_pages.scalar_type() == torch::kInt32,
               "page lists must be int32 on GPU");
   TORCH_CHECK(src_pages.numel() == dst_pages.numel(), "page count mismatch");
+  // the page indices themselves are range-checked by the caller
+  // (PeerKVPusher.push) before they are uploaded
+  TORCH_CHECK(dst_base != 0, "dst_base is null");
+  TORCH_CHECK(dst_num_pages >= 1, "dst_num_pages must be >= 1, got ",
+              dst_num_pages);
   const int n_pages = src_pages.numel();
   if (n_pages == 0) return;
   const int layers = src_kv.size(0);

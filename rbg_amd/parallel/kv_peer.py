@@ -27,6 +27,7 @@ from __future__ import annotations
 
 import base64
 import logging
+import numbers
 import threading
 import time
 from typing import Any, Dict, List
@@ -69,6 +70,38 @@ def export_meta_local(cache: PagedKVCache) -> Dict[str, Any]:
         "shape": list(cache.kv.shape),
         **cache.signature(),
     }
+
+
+def check_push_args(src_shape: List[int], src_pages: List[int],
+                    dst_meta: Dict[str, Any], dst_pages: List[int]) -> None:
+    """Raise ValueError unless the push is one the copy kernel can run
+    as given: pools that differ in the page count alone, every index inside
+    its pool, and no destination page named twice (two blocks would race
+    on it)."""
+    dst_shape = [int(d) for d in dst_meta["shape"]]
+    num_pages = int(dst_meta["num_pages"])
+    if len(dst_shape) != 6 or len(src_shape) != 6:
+        raise ValueError(f"KV pools are 6-D, got {src_shape} -> {dst_shape}")
+    if dst_shape[:2] + dst_shape[3:] != src_shape[:2] + src_shape[3:]:
+        raise ValueError(
+            "peer push between pools of different layout: "
+            f"{src_shape} here vs {dst_shape} on the peer (only the page "
+            "count may differ)")
+    if num_pages != dst_shape[2] or num_pages < 1:
+        raise ValueError(f"peer pool reports num_pages {num_pages} but "
+                         f"shape {dst_shape}")
+    if len(src_pages) != len(dst_pages):
+        raise ValueError(f"{len(src_pages)} source pages for "
+                         f"{len(dst_pages)} destination pages")
+    for what, pages, limit in (("source", src_pages, src_shape[2]),
+                               ("destination", dst_pages, num_pages)):
+        bad = [p for p in pages
+               if isinstance(p, bool) or not isinstance(p, numbers.Integral)
+               or not 0 <= p < limit]
+        if bad:
+            raise ValueError(f"{what} pages {bad[:8]} outside [0, {limit})")
+    if len(set(dst_pages)) != len(dst_pages):
+        raise ValueError("a destination page is named twice in one push")
 
 
 class PeerDead(RuntimeError):
@@ -187,17 +220,18 @@ class PeerKVPusher:
         """Launch the peer copy; returns immediately with a PendingPush.
         The copy runs on this pusher's dedicated stream so it overlaps any
         compute the caller's engine keeps issuing on the default stream."""
-        assert len(src_pages) == len(dst_pages)
         # element type and exponents first: the copy moves raw bytes
         from .comm import check_kv_signature
         check_kv_signature(cache.signature(), dst_meta, "peer push")
+        shape = cache.kv.shape
+        # the kernel trusts every index: a page >= the pool's page count
+        # lands in the next (layer, K|V) plane or past the pool, so all of
+        # this is refused on the host, before anything is mapped or launched
+        check_push_args(list(shape), src_pages, dst_meta, dst_pages)
         uid = str(dst_meta.get("uid", dst_meta.get("local_ptr", "")))
         with self._lock:
             if uid in self._bad:
                 raise PeerDead(f"pool {uid} is quarantined (dead peer)")
-        shape = cache.kv.shape
-        assert list(shape)[3:] == list(dst_meta["shape"])[3:], \
-            "page layout mismatch between src and dst pools"
         dst_base = self._map(dst_meta)
         chunk_bytes = (shape[3] * shape[4] * shape[5] *
                        cache.kv.element_size())

@@ -81,10 +81,11 @@ def model_config(conf: str) -> ModelConfig:
     raise ValueError(conf)
 
 
-def engine_config(conf: str, device: str, eager: bool, **kw) -> EngineConfig:
+def engine_config(conf: str, device: str, eager: bool,
+                  pool_tokens: int = POOL_TOKENS, **kw) -> EngineConfig:
     return EngineConfig(model=model_config(conf), device=device,
                         page_size=PAGE, max_seq_len=MAX_SEQ_LEN,
-                        kv_pool_tokens=POOL_TOKENS, enforce_eager=eager, **kw)
+                        kv_pool_tokens=pool_tokens, enforce_eager=eager, **kw)
 
 
 # ---------------------------------------------------------------------------
@@ -283,6 +284,7 @@ class SeqRecord:
         self.seq = seq
         self.weights = weights          # index into Recorder.weights
         self.rows: List[Tuple[int, torch.Tensor]] = []   # (num_tokens, logits)
+        self.sampled: List[int] = []    # the token drawn from each row
         self.pages: List[int] = []
         self.final_kv: Optional[torch.Tensor] = None
         self.final_count = 0
@@ -329,7 +331,10 @@ class Recorder:
                     rec.final_count = seq.num_tokens
                     rec.final_kv = gather_rows(self.runner.cache.kv,
                                                rec.pages, seq.num_tokens)
-            return sample(logits, seqs)
+            out = sample(logits, seqs)
+            for seq, tok in zip(seqs, out[1]):
+                self.seqs[seq.seq_id].sampled.append(int(tok))
+            return out
 
         def decode_(seqs):
             self.decode_batches.append(tuple(s.seq_id for s in seqs))
@@ -382,10 +387,11 @@ class Trace:
             self.prefill.append(list(zip(lq, lk)))
             return prefill(q, k, v, cu, scale, cu_k)
 
-        def decode_(q, kc, vc, bt, ctx, scale, num_splits=0, variant=-1):
+        def decode_(q, kc, vc, bt, ctx, scale, num_splits=0, variant=-1,
+                    **fp8_exponents):
             self.decode.append((int(q.shape[0]), int(num_splits)))
             return decode(q, kc, vc, bt, ctx, scale, num_splits=num_splits,
-                          variant=variant)
+                          variant=variant, **fp8_exponents)
 
         ops.linear, ops.prefill_attention, ops.decode_attention = \
             linear_, prefill_, decode_
