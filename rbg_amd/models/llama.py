@@ -189,7 +189,11 @@ class LlamaAttention(nn.Module):
                                        requires_grad=False)
 
     def forward(self, x: torch.Tensor, batch: ForwardBatch,
-                kv: PagedKVCache, cos_sin: torch.Tensor) -> torch.Tensor:
+                kv: PagedKVCache, cos_sin: torch.Tensor,
+                add_norm=None) -> torch.Tensor:
+        """add_norm = (residual, norm_weight, eps) fuses the residual add and
+        the following RMSNorm into o_proj (TP = 1 only: no all-reduce sits
+        between them); the return value is then the normed hidden state."""
         T = x.shape[0]
         qkv = ops.linear(x, self.wqkv)
         # q/k/v stay SLICES of the fused projection: the rope and attention
@@ -261,8 +265,10 @@ class LlamaAttention(nn.Module):
                                      batch.block_tables, batch.context_lens,
                                      self.scale,
                                      num_splits=batch.decode_num_splits)
-        out = ops.linear(o.view(T, self.q_out).contiguous(), self.wo)
-        return self.tp.all_reduce(out)
+        o = o.view(T, self.q_out).contiguous()
+        if add_norm is not None:
+            return ops.linear_add_rmsnorm(o, self.wo, *add_norm)
+        return self.tp.all_reduce(ops.linear(o, self.wo))
 
 
 class LlamaMLP(nn.Module):
@@ -284,9 +290,12 @@ class LlamaMLP(nn.Module):
                                      tp_size=tp.size, tp_rank=tp.rank)
         self.inter = inter
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, add_norm=None) -> torch.Tensor:
+        """add_norm: as in LlamaAttention.forward, fused into down_proj."""
         gu = ops.linear(x, self.w_gate_up)
         h = ops.silu_mul(gu)
+        if add_norm is not None:
+            return ops.linear_add_rmsnorm(h, self.w_down, *add_norm)
         return self.tp.all_reduce(ops.linear(h, self.w_down))
 
 
@@ -305,6 +314,14 @@ class LlamaLayer(nn.Module):
             torch.ones(cfg.hidden_size, device=device, dtype=dtype),
             requires_grad=False)
         self.eps = cfg.rms_eps
+        # With TP = 1 nothing sits between a row-parallel projection and the
+        # add + norm behind it, so o_proj takes post_norm and down_proj the
+        # NEXT local layer's input_norm (ops.linear_add_rmsnorm).  Set by
+        # LlamaForCausalLM.link_norm_fusion; held in a tuple so the next
+        # layer's parameter is not registered a second time here.
+        self.fuse_norms = False
+        self.next_input_norm: tuple = ()
+        self.input_prenormed = False
 
     def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor],
                 batch: ForwardBatch, kv: PagedKVCache,
@@ -312,14 +329,26 @@ class LlamaLayer(nn.Module):
         if residual is None:
             residual = x.clone()
             h = ops.rmsnorm(x, self.input_norm, self.eps)
+        elif self.input_prenormed:
+            # the previous layer's down_proj added into residual and applied
+            # this layer's input_norm already
+            h = x
         else:
             # h := rmsnorm(x + residual); residual := x + residual  (fused)
             ops.fused_add_rmsnorm(x, residual, self.input_norm, self.eps)
             h = x
-        h = self.attn(h, batch, kv, cos_sin)
-        ops.fused_add_rmsnorm(h, residual, self.post_norm, self.eps)
-        h = self.mlp(h)
-        return h, residual
+        if not self.fuse_norms:
+            h = self.attn(h, batch, kv, cos_sin)
+            ops.fused_add_rmsnorm(h, residual, self.post_norm, self.eps)
+            return self.mlp(h), residual
+        h = self.attn(h, batch, kv, cos_sin,
+                      add_norm=(residual, self.post_norm, self.eps))
+        if self.next_input_norm:
+            return self.mlp(h, add_norm=(residual, self.next_input_norm[0],
+                                         self.eps)), residual
+        # a stage's last layer: the model's final x + residual rounds before
+        # it squares, so fusing a norm here would change bits
+        return self.mlp(h), residual
 
 
 class LlamaForCausalLM(nn.Module):
@@ -359,6 +388,7 @@ class LlamaForCausalLM(nn.Module):
             LlamaLayer(cfg, i - self.layer_start, self.tp, device, dtype,
                        _gen(1 + i))
             for i in range(self.layer_start, self.layer_end)])
+        self.link_norm_fusion(self.tp.size == 1)
         self.final_norm = None
         self.lm_head = None
         if self.pp.last:
@@ -370,6 +400,17 @@ class LlamaForCausalLM(nn.Module):
         self.cos_sin = ops.build_cos_sin_table(
             cfg.head_dim, cfg.max_position, cfg.rope_theta,
             device=device)
+
+    def link_norm_fusion(self, on: bool) -> None:
+        """Fuse each row-parallel projection with the add + RMSNorm behind
+        it (LlamaLayer.fuse_norms); down_proj of local layer i applies layer
+        i+1's input_norm, so the two layers are switched together."""
+        layers = list(self.layers)
+        for i, layer in enumerate(layers):
+            nxt = layers[i + 1] if on and i + 1 < len(layers) else None
+            layer.fuse_norms = on
+            layer.input_prenormed = on and i > 0
+            layer.next_input_norm = () if nxt is None else (nxt.input_norm,)
 
     @property
     def num_local_layers(self) -> int:

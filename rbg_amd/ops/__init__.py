@@ -79,14 +79,35 @@ def linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     # on narrow-N shapes (o/down, N<=4096) at any decode batch, on mid-N
     # (qkv, 6144) only up to M=64, and never on wide-N (gate_up 28672,
     # where hipBLASLt already streams at ~6 TB/s)
-    if (SKINNY_GEMM and _on_gpu(x) and x.dim() == 2 and
-            x.dtype == torch.bfloat16 and 1 <= x.shape[0] <= 128 and
-            w.shape[0] % 32 == 0 and x.shape[1] % 512 == 0 and
-            (w.shape[0] <= 4608 or
-             (x.shape[0] <= 64 and w.shape[0] <= 8192))):
+    if _use_skinny_gemm(x, w):
         return _require_hip().skinny_gemm(
             x if x.is_contiguous() else x.contiguous(), w)
     return torch.nn.functional.linear(x, w)
+
+
+def _use_skinny_gemm(x: torch.Tensor, w: torch.Tensor) -> bool:
+    return bool(SKINNY_GEMM and _on_gpu(x) and x.dim() == 2 and
+                x.dtype == torch.bfloat16 and 1 <= x.shape[0] <= 128 and
+                w.shape[0] % 32 == 0 and x.shape[1] % 512 == 0 and
+                (w.shape[0] <= 4608 or
+                 (x.shape[0] <= 64 and w.shape[0] <= 8192)))
+
+
+def linear_add_rmsnorm(x: torch.Tensor, w: torch.Tensor,
+                       residual: torch.Tensor, norm_weight: torch.Tensor,
+                       eps: float) -> torch.Tensor:
+    """h = linear(x, w); residual += h; return rmsnorm(residual) — bit for
+    bit `h = linear(x, w); fused_add_rmsnorm(h, residual, ...)`.  Where
+    linear() would take the custom GEMM, the split-K partials are folded
+    inside the norm kernel instead of by a reduce launch of their own
+    (hip/rmsnorm.hip, NORM_FOLD_ADD)."""
+    if _use_skinny_gemm(x, w):
+        return _require_hip().skinny_gemm_add_rmsnorm(
+            x if x.is_contiguous() else x.contiguous(), w, residual,
+            norm_weight, eps)
+    h = linear(x, w)
+    fused_add_rmsnorm(h, residual, norm_weight, eps)
+    return h
 
 
 def rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float) -> torch.Tensor:

@@ -30,7 +30,11 @@ void launch_mfma_probe32(void*, const void*, const void*, int, int, int,
                          hipStream_t);
 void launch_skinny_gemm(void*, void*, const void*, const void*, int, int,
                         int, int, hipStream_t);
+void launch_skinny_gemm_wide(void*, void*, const void*, const void*, int, int,
+                             int, int, hipStream_t);
 void launch_reduce_splits(void*, const void*, int, long, hipStream_t);
+void launch_fold_add_rmsnorm(void*, const void*, void*, const void*, float,
+                             int, int, int, hipStream_t);
 void launch_kv_peer_copy(void*, const void*, const void*, const void*, int,
                          int, int, long, long, long, long, hipStream_t);
 void launch_xgmi_allreduce(void*, const void*, void**, void**, int, int,
@@ -473,8 +477,31 @@ bool skinny_gemm_supported(int64_t M, int64_t N, int64_t K) {
   return M >= 1 && M <= 256 && (N % 32) == 0 && (K % 256) == 0;
 }
 
-torch::Tensor skinny_gemm(torch::Tensor a, torch::Tensor w,
-                          int64_t force_splits = 0) {
+// The 64-column-panel kernel (skinny_gemm_wide_kernel): 8 waves over
+// 4 row groups of at most 2 m-tiles, whole 64-column panels.
+bool skinny_gemm_wide_supported(int64_t M, int64_t N) {
+  return M >= 1 && M <= 128 && (N % 64) == 0;
+}
+
+static int pick_gemm_panel(int64_t M, int64_t N) {
+  // measured policy (profiles/sg_micro8_cold.json, weights streamed from
+  // HBM, o and down of Llama-3-8B): the 64-column panel wins at M = 64
+  // (o 14.5 -> 12.9 us, down 35.1 -> 28.4) and M = 128 (o 20.4 -> 15.9,
+  // down 50.8 -> 36.1); at M <= 32, where A is at most a fifth of a
+  // 32-column panel's staging anyway, it ties or loses by up to 7 %
+  // (o at M = 16: 11.4 -> 12.2)
+  return M > 32 && skinny_gemm_wide_supported(M, N) ? 64 : 32;
+}
+
+namespace {
+
+// Shape, dtype, device and contiguity checks shared by skinny_gemm and
+// skinny_gemm_add_rmsnorm, then the GEMM launch.  Returns the split count;
+// with splits > 1 the f32 partials [splits, M, N] are left in `ws` for the
+// caller to fold, with splits == 1 the bf16 result is in `c`.
+int skinny_gemm_launch(const torch::Tensor& a, const torch::Tensor& w,
+                       int64_t force_splits, int64_t panel, torch::Tensor& c,
+                       torch::Tensor& ws) {
   check_bf16_contig(a, "a");
   check_bf16_contig(w, "w");
   TORCH_CHECK(a.dim() == 2 && w.dim() == 2, "a and w must be 2-D");
@@ -490,22 +517,78 @@ torch::Tensor skinny_gemm(torch::Tensor a, torch::Tensor w,
               "force_splits must be 0 (auto), 1, 2, 4 or 8");
   TORCH_CHECK(force_splits == 0 || K % (force_splits * 256) == 0,
               "K must be a multiple of force_splits * 256");
-  auto c = torch::empty({M, N}, a.options());
+  TORCH_CHECK(panel == 0 || panel == 32 || panel == 64,
+              "panel must be 0 (auto), 32 or 64");
+  TORCH_CHECK(panel != 64 || skinny_gemm_wide_supported(M, N),
+              "panel 64 needs M <= 128 and N % 64 == 0");
   const int splits = force_splits > 0 ? (int)force_splits
                                       : pick_gemm_splits((int)N, (int)K);
-  torch::Tensor ws;
+  if (panel == 0) panel = pick_gemm_panel(M, N);
+  void* cp = nullptr;
   void* wsp = nullptr;
   if (splits > 1) {
     ws = torch::empty({splits, M, N}, a.options().dtype(torch::kFloat32));
     wsp = ws.data_ptr();
+  } else {
+    c = torch::empty({M, N}, a.options());
+    cp = c.data_ptr();
   }
-  launch_skinny_gemm(c.data_ptr(), wsp, a.data_ptr(), w.data_ptr(), (int)M,
-                     (int)N, (int)K, splits, current_stream());
-  if (splits > 1)
-    launch_reduce_splits(c.data_ptr(), wsp, splits, (long)(M * N),
-                         current_stream());
+  (panel == 64 ? launch_skinny_gemm_wide : launch_skinny_gemm)(
+      cp, wsp, a.data_ptr(), w.data_ptr(), (int)M, (int)N, (int)K, splits,
+      current_stream());
+  return splits;
+}
+
+}  // namespace
+
+torch::Tensor skinny_gemm(torch::Tensor a, torch::Tensor w,
+                          int64_t force_splits = 0, int64_t panel = 0) {
+  torch::Tensor c, ws;
+  const int splits = skinny_gemm_launch(a, w, force_splits, panel, c, ws);
+  if (splits > 1) {
+    c = torch::empty({a.size(0), w.size(0)}, a.options());
+    launch_reduce_splits(c.data_ptr(), ws.data_ptr(), splits,
+                         (long)c.numel(), current_stream());
+  }
   return c;
 }
+
+// h = rmsnorm(a w^T + residual) * norm_weight with residual := a w^T +
+// residual in place: bit for bit skinny_gemm followed by fused_add_rmsnorm,
+// but the split-K fold happens in the norm kernel's prologue instead of a
+// reduce_splits launch (and a bf16 round trip) of its own.
+torch::Tensor skinny_gemm_add_rmsnorm(torch::Tensor a, torch::Tensor w,
+                                      torch::Tensor residual,
+                                      torch::Tensor norm_weight, double eps,
+                                      int64_t force_splits = 0,
+                                      int64_t panel = 0) {
+  check_bf16_contig(residual, "residual");
+  check_bf16_contig(norm_weight, "norm_weight");
+  TORCH_CHECK(a.dim() == 2 && w.dim() == 2, "a and w must be 2-D");
+  TORCH_CHECK(residual.dim() == 2 && residual.size(0) == a.size(0) &&
+                  residual.size(1) == w.size(0),
+              "residual must be [M, N]");
+  TORCH_CHECK(norm_weight.numel() == w.size(0),
+              "norm_weight must have N elements");
+  TORCH_CHECK(residual.device() == a.device() &&
+                  norm_weight.device() == a.device(),
+              "a/residual/norm_weight device mismatch");
+  torch::Tensor c, ws;
+  const int splits = skinny_gemm_launch(a, w, force_splits, panel, c, ws);
+  const int M = (int)a.size(0), N = (int)w.size(0);
+  if (splits == 1) {
+    launch_fused_add_rmsnorm(c.data_ptr(), residual.data_ptr(),
+                             norm_weight.data_ptr(), (float)eps, M, N,
+                             current_stream());
+    return c;
+  }
+  c = torch::empty({a.size(0), w.size(0)}, a.options());
+  launch_fold_add_rmsnorm(c.data_ptr(), ws.data_ptr(), residual.data_ptr(),
+                          norm_weight.data_ptr(), (float)eps, splits, M, N,
+                          current_stream());
+  return c;
+}
+
 
 // ---- fused seeded sampler (ops.sample) -----------------------------------
 // logits fp32 [n, V] contiguous; every per-row parameter is a device tensor
@@ -735,7 +818,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mfma_probe", &mfma_probe, "MFMA layout probe");
   m.def("mfma_probe32", &mfma_probe32, "32x32x16 MFMA layout probe");
   m.def("skinny_gemm", &skinny_gemm, "decode-shape GEMM (M<=128)",
-        py::arg("a"), py::arg("w"), py::arg("force_splits") = 0);
+        py::arg("a"), py::arg("w"), py::arg("force_splits") = 0,
+        py::arg("panel") = 0);
+  m.def("skinny_gemm_add_rmsnorm", &skinny_gemm_add_rmsnorm,
+        "skinny_gemm + fused_add_rmsnorm with the split-K fold inside the "
+        "norm kernel; returns h, updates residual in place",
+        py::arg("a"), py::arg("w"), py::arg("residual"),
+        py::arg("norm_weight"), py::arg("eps"), py::arg("force_splits") = 0,
+        py::arg("panel") = 0);
   m.def("sample", &sample,
         "seeded top-k/min-p/top-p Gumbel-max sampler -> (tokens, num_kept)");
   // gil_scoped_release on the IPC/copy entry points: mapping or launching

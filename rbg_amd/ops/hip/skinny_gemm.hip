@@ -24,12 +24,19 @@
 //   math  = per step each wave reads 1 W + M_TILES A fragments from LDS
 //           (contiguous-8 per-lane MFMA layout) and issues M_TILES MFMAs
 //   end   = the 2 k-slices of each n-tile fold through the LDS reduce
-//           scratch, one bf16 store; SPLITS>1 writes f32 partials +
-//           reduce_splits() folds them
+//           scratch, one bf16 store; SPLITS>1 writes f32 partials, folded
+//           by reduce_splits() or, where an add + RMSNorm follows, inside
+//           that kernel (rmsnorm.hip, NORM_FOLD_ADD)
 //
 // A-traffic note: a 32-column panel reads all of A (M x K, ~1 MB at
 // M=128/K=4096) — L2-resident after the first panel per XCD, so HBM sees
-// ~W + 8 x A bytes.
+// only ~W + 8 x A bytes.  On chip it is the other way round: per 64-k step
+// a workgroup moves 4 KB of W and M x 128 B of A (16 KB at M = 128) from
+// L2 into LDS, so 4/5 of the CU's L2->LDS fill (and of its ds_write
+// traffic) is A.  That fill, not HBM, bounds this kernel at large M; the
+// 64-column kernel below halves the A share and is the one dispatched for
+// M <= 128, N % 64 == 0 where it measured faster (bindings.cpp).  This
+// kernel stays for N % 64 != 0 and M > 128.
 #include "common.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 gg_bf8;
@@ -231,6 +238,198 @@ __global__ __launch_bounds__(SG_NT, 3) void skinny_gemm_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// 64-column-panel kernel for M <= 128, N % 64 == 0 (decode o/down).
+//
+// Why: a CU fills LDS from an L2-resident source at a fixed ~70 GB/s, and
+// the 32-column kernel above spends 4/5 of that fill on A (16 KB of A per
+// 4 KB of W per step at M = 128).  Owning 64 columns stages A once per
+// 8 KB of W, so the same fill rate carries twice the weight stream.
+//
+//   grid  = (N/64) * SPLITS workgroups of 8 waves: (k_slice 0..1) x
+//           (4 row groups of MTW m-tiles); each wave holds MTW x 4 n-tile
+//           accumulators, so an A fragment feeds 4 MFMAs and a W fragment
+//           MTW.  MTW = 1 serves M <= 64 (64 staged rows), MTW = 2 M <= 128
+//   pipe  = the same double-buffered LDS with one barrier per step.  A (L2)
+//           rides two named register sets 2-3 steps ahead as above; W (HBM)
+//           rides a ring of FOUR named registers 4-5 steps ahead, because
+//           one workgroup per CU at twice the step rate halves the time a
+//           2-deep set would give an HBM miss to land.  A is issued before W
+//           in every step so the in-order vmcnt wait for A(t+1) never waits
+//           on the younger W loads
+//   end   = k_slice 1 hands its accumulators to k_slice 0 through LDS
+//
+// Bit-identical to skinny_gemm_kernel at equal (M, N, K, SPLITS): every
+// output element is the same two MFMA chains (k offsets [0,32) and [32,64)
+// of each step, in step order) added in f32; which wave owns a chain is the
+// only difference.
+#define SGW_NT 512                    // threads (8 waves)
+
+template <int MTW, int SPLITS>
+__global__ __launch_bounds__(SGW_NT) void skinny_gemm_wide_kernel(
+    const __hip_bfloat16* __restrict__ a,   // [M, K]
+    const __hip_bfloat16* __restrict__ w,   // [N, K]
+    __hip_bfloat16* __restrict__ c,         // [M, N]   (SPLITS == 1)
+    float* __restrict__ ws,                 // [SPLITS, M, N] (SPLITS > 1)
+    const int M, const int N, const int K) {
+  const int n_groups = N >> 6;
+  const int n_group = blockIdx.x % n_groups;
+  const int split = blockIdx.x / n_groups;
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6;
+  const int lane = tid & 63;
+  const int gl = lane & 15;
+  const int gslice = lane >> 4;
+
+  const int row_group = wave & 3;            // MTW m-tiles each
+  const int k_slice = wave >> 2;             // 0..1, 32 k each per step
+  const int k_wg = K / SPLITS;
+  const int k0 = split * k_wg;
+  const int nsteps = k_wg / SG_KSTEP;        // multiple of 4 (host-side)
+
+  constexpr int A_ROWS = MTW * 64;
+  constexpr int BUF = (64 + A_ROWS) * SG_LDS_PITCH;
+  __shared__ union {
+    __hip_bfloat16 stage[2][BUF];
+    float red[4][MTW * 4 * 256];
+  } lds;
+
+  // staging pieces of 16 B: W = 64 rows x 8 chunks = one per thread, A =
+  // A_ROWS x 8 = MTW per thread (piece s is row (tid >> 3) + 64 * s)
+  const int srow = tid >> 3, schk = (tid & 7) * 8;
+  const __hip_bfloat16* wbase =
+      w + (size_t)((n_group << 6) + srow) * K + schk;
+  const __hip_bfloat16* ab0 = a + (size_t)min(srow, M - 1) * K + schk;
+  const __hip_bfloat16* ab1 = a + (size_t)min(srow + 64, M - 1) * K + schk;
+
+  uint4 w0, w1, w2, w3;
+  uint4 a00, a01 = {}, a10, a11 = {};
+
+#define SGW_KB(step) (k0 + min(step, nsteps - 1) * SG_KSTEP)
+#define SGW_LD(p, kb) (*reinterpret_cast<const uint4*>((p) + (kb)))
+#define SGW_ISSUE_A(step, x0, x1)                                           \
+  do {                                                                      \
+    const int kb = SGW_KB(step);                                            \
+    x0 = SGW_LD(ab0, kb);                                                   \
+    if (MTW > 1) x1 = SGW_LD(ab1, kb);                                      \
+  } while (0)
+#define SGW_ISSUE_W(step, wr) wr = SGW_LD(wbase, SGW_KB(step))
+#define SGW_WRITE(st, wr, x0, x1)                                           \
+  do {                                                                      \
+    *reinterpret_cast<uint4*>(&st[srow * SG_LDS_PITCH + schk]) = wr;        \
+    *reinterpret_cast<uint4*>(&st[(64 + srow) * SG_LDS_PITCH + schk]) = x0; \
+    if (MTW > 1)                                                            \
+      *reinterpret_cast<uint4*>(&st[(128 + srow) * SG_LDS_PITCH + schk]) =  \
+          x1;                                                               \
+  } while (0)
+
+  f32x4 acc[MTW][4];
+#pragma unroll
+  for (int mt = 0; mt < MTW; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = {0.f, 0.f, 0.f, 0.f};
+
+  const int kf = k_slice * 32 + gslice * 8;
+  auto compute = [&](const __hip_bfloat16* st) {
+    const gg_bf8 wf0 = lds_frag(&st[gl * SG_LDS_PITCH + kf]);
+    const gg_bf8 wf1 = lds_frag(&st[(16 + gl) * SG_LDS_PITCH + kf]);
+    const gg_bf8 wf2 = lds_frag(&st[(32 + gl) * SG_LDS_PITCH + kf]);
+    const gg_bf8 wf3 = lds_frag(&st[(48 + gl) * SG_LDS_PITCH + kf]);
+#pragma unroll
+    for (int mt = 0; mt < MTW; ++mt) {
+      const gg_bf8 af = lds_frag(
+          &st[(64 + (row_group * MTW + mt) * 16 + gl) * SG_LDS_PITCH + kf]);
+      acc[mt][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, wf0,
+                                                           acc[mt][0], 0, 0, 0);
+      acc[mt][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, wf1,
+                                                           acc[mt][1], 0, 0, 0);
+      acc[mt][2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, wf2,
+                                                           acc[mt][2], 0, 0, 0);
+      acc[mt][3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, wf3,
+                                                           acc[mt][3], 0, 0, 0);
+    }
+  };
+
+  __hip_bfloat16* buf0 = lds.stage[0];
+  __hip_bfloat16* buf1 = lds.stage[1];
+
+  // prologue: A tiles 0,1 and W tiles 0..3 in flight; tile 0 lands in
+  // buffer 0 and its registers are re-issued
+  SGW_ISSUE_A(0, a00, a01);
+  SGW_ISSUE_W(0, w0);
+  SGW_ISSUE_A(1, a10, a11);
+  SGW_ISSUE_W(1, w1);
+  SGW_ISSUE_W(2, w2);
+  SGW_ISSUE_W(3, w3);
+  SGW_WRITE(buf0, w0, a00, a01);
+  SGW_ISSUE_A(2, a00, a01);
+  SGW_ISSUE_W(4, w0);
+
+  // step t: compute tile t, write tile t+1 (W ring slot (t+1)&3, A set
+  // (t+1)&1) into the other buffer, re-issue those registers for A tile
+  // t+3 and W tile t+5.  A buffer's previous tile was fully read before
+  // the barrier, so one barrier per step suffices
+#define SGW_STEP(t, cur, nxt, wr, x0, x1)                                   \
+  do {                                                                      \
+    __syncthreads();                                                        \
+    compute(cur);                                                           \
+    SGW_WRITE(nxt, wr, x0, x1);                                             \
+    SGW_ISSUE_A((t) + 3, x0, x1);                                           \
+    SGW_ISSUE_W((t) + 5, wr);                                               \
+  } while (0)
+  for (int step = 0; step < nsteps; step += 4) {
+    SGW_STEP(step, buf0, buf1, w1, a10, a11);
+    SGW_STEP(step + 1, buf1, buf0, w2, a00, a01);
+    SGW_STEP(step + 2, buf0, buf1, w3, a10, a11);
+    SGW_STEP(step + 3, buf1, buf0, w0, a00, a01);
+  }
+#undef SGW_STEP
+#undef SGW_WRITE
+#undef SGW_ISSUE_W
+#undef SGW_ISSUE_A
+#undef SGW_LD
+#undef SGW_KB
+
+  // ---- fold the two k-slices: slice 1 -> LDS -> slice 0 adds and stores --
+  __syncthreads();
+  if (k_slice == 1) {
+#pragma unroll
+    for (int mt = 0; mt < MTW; ++mt)
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) {
+        F32x4U u;
+        u.v = acc[mt][nt];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          lds.red[row_group][(mt * 4 + nt) * 256 + r * 64 + lane] = u.e[r];
+      }
+  }
+  __syncthreads();
+  if (k_slice == 0) {
+    // MFMA C layout: reg r of lane l is row 4*(l>>4)+r, column l&15
+#pragma unroll
+    for (int mt = 0; mt < MTW; ++mt)
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) {
+        F32x4U u;
+        u.v = acc[mt][nt];
+        const int n = (n_group << 6) + (nt << 4) + gl;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float v =
+              u.e[r] + lds.red[row_group][(mt * 4 + nt) * 256 + r * 64 + lane];
+          const int m = (row_group * MTW + mt) * 16 + (gslice << 2) + r;
+          if (m < M) {
+            if (SPLITS == 1)
+              c[(size_t)m * N + n] = f2bf(v);
+            else
+              ws[((size_t)split * M + m) * N + n] = v;
+          }
+        }
+      }
+  }
+}
+
 __global__ void reduce_splits_kernel(const float* __restrict__ ws,
                                      __hip_bfloat16* __restrict__ c,
                                      const int splits, const long mn) {
@@ -276,6 +475,37 @@ extern "C" void launch_skinny_gemm(void* c, void* ws, const void* a,
   else if (m_tiles <= 8) LAUNCH_MT(8);
   else LAUNCH_MT(16);
 #undef LAUNCH_MT
+}
+
+// M <= 128 and N % 64 == 0 (checked in bindings.cpp)
+extern "C" void launch_skinny_gemm_wide(void* c, void* ws, const void* a,
+                                        const void* w, int M, int N, int K,
+                                        int splits, hipStream_t stream) {
+  const dim3 grid((N >> 6) * splits), block(SGW_NT);
+  const __hip_bfloat16* ap = (const __hip_bfloat16*)a;
+  const __hip_bfloat16* wp = (const __hip_bfloat16*)w;
+  __hip_bfloat16* cp = (__hip_bfloat16*)c;
+  float* wsp = (float*)ws;
+
+#define LAUNCH_MTW(MTW)                                                      \
+  do {                                                                       \
+    if (splits == 1)                                                         \
+      skinny_gemm_wide_kernel<MTW, 1><<<grid, block, 0, stream>>>(           \
+          ap, wp, cp, nullptr, M, N, K);                                     \
+    else if (splits == 2)                                                    \
+      skinny_gemm_wide_kernel<MTW, 2><<<grid, block, 0, stream>>>(           \
+          ap, wp, cp, wsp, M, N, K);                                         \
+    else if (splits == 4)                                                    \
+      skinny_gemm_wide_kernel<MTW, 4><<<grid, block, 0, stream>>>(           \
+          ap, wp, cp, wsp, M, N, K);                                         \
+    else                                                                     \
+      skinny_gemm_wide_kernel<MTW, 8><<<grid, block, 0, stream>>>(           \
+          ap, wp, cp, wsp, M, N, K);                                         \
+  } while (0)
+
+  if (M <= 64) LAUNCH_MTW(1);
+  else LAUNCH_MTW(2);
+#undef LAUNCH_MTW
 }
 
 extern "C" void launch_reduce_splits(void* c, const void* ws, int splits,
