@@ -1,7 +1,7 @@
 # rbg-mi355x developer entry points
 PY ?= python
 
-.PHONY: build test test-gpu bench serve stress clean
+.PHONY: build test test-gpu check-kernels bench serve stress clean
 
 build:            ## compile the gfx950 HIP extension in-tree
 	PYTORCH_ROCM_ARCH=gfx950 $(PY) setup.py build_ext --inplace
@@ -11,6 +11,9 @@ test:             ## CPU suite (tiny model, gloo)
 
 test-gpu:         ## MI355X suite (kernel numerics + GPU serving e2e)
 	$(PY) -m pytest tests/ -q -m gpu
+
+check-kernels:    ## hipcc only, ~1 min: decode kernels' registers, scratch, pair-loop order
+	$(PY) tools/decode_loop_compare.py --check
 
 bench:            ## driver-contract benchmark, 1 GPU
 	$(PY) bench.py --steps 30 --warmup 10

@@ -213,7 +213,13 @@ PREFILL_SWZ = int(os.environ.get("RBG_PREFILL_SWZ", "6"))  # 8-wave + K/V double
 def decode_attention(q, key_cache, value_cache, block_tables, context_lens,
                      scale: float, num_splits: int = 0,
                      variant: int = -1, k_scale_log2: int = 0,
-                     v_scale_log2: int = 0) -> torch.Tensor:
+                     v_scale_log2: int = 0, combine: int = 0) -> torch.Tensor:
+    """Paged flash-decode.  combine says how the partials of num_splits > 1
+    are merged on the GPU: 0 picks (inside the workgroup for the page-pair
+    MFMA kernels at 2 or 4 splits, where the splits are the waves of one
+    workgroup and neither partials nor a second launch exist; else by
+    decode_combine_kernel), 1 forces the separate kernel, 2 the in-workgroup
+    merge (raising where no kernel has it).  Both give the same bits."""
     if _is_fp8_pair(key_cache, value_cache):
         # one kernel reads an e4m3 cache: the page-pair MFMA one (variant 4)
         if variant not in (-1, 4):
@@ -233,7 +239,7 @@ def decode_attention(q, key_cache, value_cache, block_tables, context_lens,
                                                 key_cache.shape[1], max_ctx, 4)
             return _require_hip().decode_attention_fp8(
                 q, key_cache, value_cache, block_tables, context_lens, scale,
-                num_splits, k_scale_log2, v_scale_log2)
+                num_splits, k_scale_log2, v_scale_log2, combine)
         return reference.decode_attention(
             q, key_cache, value_cache, block_tables, context_lens, scale,
             k_scale_log2, v_scale_log2)
@@ -246,7 +252,7 @@ def decode_attention(q, key_cache, value_cache, block_tables, context_lens,
             variant = DECODE_VARIANT
         return _require_hip().decode_attention(
             q, key_cache, value_cache, block_tables, context_lens, scale,
-            num_splits, variant)
+            num_splits, variant, combine)
     return reference.decode_attention(q, key_cache, value_cache, block_tables,
                                       context_lens, scale)
 

@@ -320,6 +320,25 @@ void decode_attn_kernel(
 constexpr int DM_KP = 132;      // K panel pitch (bf16)
 constexpr int DM_PP = 40;       // P tile pitch (bf16)
 
+// Merge of the splits' (O, m, l) partials of one output element by the
+// log-sum-exp algebra, in split order.  decode_combine_kernel (partials in
+// HBM) and the in-workgroup epilogue of the MFMA kernels (partials in LDS)
+// both call it, so the two produce the same bits.  An empty split (m = -inf,
+// l = 0) contributes 0 and a ctx == 0 row comes out 0.
+template <class GetM, class GetL, class GetO>
+DEV_INLINE __hip_bfloat16 merge_splits(int num_splits, GetM m_of, GetL l_of,
+                                       GetO o_of) {
+  float m_star = NEG_INF;
+  for (int s = 0; s < num_splits; ++s) m_star = fmaxf(m_star, m_of(s));
+  float o = 0.f, lsum = 0.f;
+  for (int s = 0; s < num_splits; ++s) {
+    const float f = __expf(m_of(s) - m_star);
+    o += o_of(s) * f;
+    lsum += l_of(s) * f;
+  }
+  return f2bf(lsum > 0.f ? o / lsum : 0.f);
+}
+
 // q A-fragments: row = head (clamped), 4 k-steps of 32 dims
 template <int QPG>
 DEV_INLINE void load_q_frags(bf8 (&qa)[4], const __hip_bfloat16* q_seq,
@@ -425,6 +444,60 @@ DEV_INLINE void store_pair_output(float* partial_o, float* partial_ml,
   }
 }
 
+// In-workgroup split merge (WS > 1): the WS waves of the workgroup are the WS
+// splits of one (seq, kv_head).  Each wave parks the rows < QPG of its
+// (O, m, l) partial as f32 in its OWN K/V panel (QPG x 128 + 2 QPG floats, at
+// most 4.1 KB of the panel's 8.4 KB; same-wave DS ordering puts the writes
+// behind the last PV reads), one barrier, then all 64 * WS threads share the
+// QPG x 128 outputs and merge them in split order: what decode_combine_kernel
+// does with partials from HBM, without the partials or the launch.
+//
+// The kernels call this when num_splits == WS and keep store_pair_output for
+// every other multiple of WS (split = blockIdx.z * WS + wave).  The launcher
+// starts them with num_splits == WS only, yet that second branch must stay:
+// with this epilogue alone the compiler schedules the pair loop, whose source
+// is the same, in another order (V's LDS writes and their vmcnt(0) ahead of
+// the softmax, one shuffle in flight at a time), and bf16 B128 x 2048 at 2
+// splits then LOSES 5.5 us to attention + combine kernel instead of winning
+// 6.1 us (profiles/decode_fused_ab.json, both builds in one job).
+// profiles/decode_wg_combine_resources.txt has the loop-by-loop comparison;
+// after a compiler update or a change to either epilogue run
+// tools/decode_loop_compare.py --check, which fails when the order moves.
+template <int QPG, int WS>
+DEV_INLINE void merge_in_workgroup(__hip_bfloat16* out, __hip_bfloat16* panels,
+                                   const f32x4 (&acc_o)[8], const float (&m)[4],
+                                   const float (&l)[4], int wave, int seq,
+                                   int kvh, int num_kv_heads, int gl,
+                                   int gslice) {
+  constexpr int PANEL_F = 32 * DM_KP / 2;     // floats per K/V panel
+  constexpr int ML = QPG * HEAD_DIM;          // m at ML + h, l at ML + QPG + h
+  static_assert(ML + 2 * QPG <= PANEL_F, "partial does not fit the panel");
+  float* part = reinterpret_cast<float*>(panels);
+  float* mine = part + wave * PANEL_F;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = 4 * gslice + r;
+    if (row >= QPG) continue;
+#pragma unroll
+    for (int dt = 0; dt < 8; ++dt)
+      mine[row * HEAD_DIM + dt * 16 + gl] = acc_o[dt][r];
+    if (gl == 0) {
+      mine[ML + row] = m[r];
+      mine[ML + QPG + row] = l[r];
+    }
+  }
+  __syncthreads();
+  const int num_q_heads = num_kv_heads * QPG;
+  for (int i = threadIdx.x; i < QPG * HEAD_DIM; i += 64 * WS) {
+    const int h = i / HEAD_DIM, d = i % HEAD_DIM;
+    out[((size_t)seq * num_q_heads + kvh * QPG + h) * HEAD_DIM + d] =
+        merge_splits(
+            WS, [&](int s) { return part[s * PANEL_F + ML + h]; },
+            [&](int s) { return part[s * PANEL_F + ML + QPG + h]; },
+            [&](int s) { return part[s * PANEL_F + h * HEAD_DIM + d]; });
+  }
+}
+
 // Global -> LDS staging of one page pair.  The lane covers K/V key row
 // srow = lane>>1 (32 rows: page myloc = srow>>4 of the pair) and the 64-elem
 // chunk schunk = (lane&1)*64, i.e. 8 x 16 B pieces; 2 lanes x 128 B = one
@@ -482,8 +555,14 @@ DEV_INLINE void store_pair_output(float* partial_o, float* partial_ml,
 // The diet does not fit 128 VGPRs cleanly: with the compiler in this tree all
 // four DIET instantiations spill (36-60 B of scratch per lane, see
 // profiles/attn_refactor_resources.txt); variant 4 has no scratch.
-template <int QPG, int DIET>
-__global__ __launch_bounds__(128, DIET ? 4 : 3) void decode_attn_mfma_kernel(
+// WS (workgroup splits): 1 is the layout above, with the split in blockIdx.z
+// and decode_combine_kernel behind it when num_splits > 1.  WS = 2 or 4
+// (variant 4) makes WS splits of ONE sequence the waves of a workgroup, grid
+// (KVH, num_seqs, num_splits / WS); with num_splits == WS they merge in LDS
+// (merge_in_workgroup): no partials in HBM, no second launch.
+template <int QPG, int DIET, int WS = 1>
+__global__ __launch_bounds__(WS == 1 ? 128 : 64 * WS, DIET ? 4 : 3)
+void decode_attn_mfma_kernel(
     float* __restrict__ partial_o,        // [splits, seqs, QH, D]
     float* __restrict__ partial_ml,       // [splits, seqs, QH, 2]
     __hip_bfloat16* __restrict__ out,     // [seqs, QH, D] (splits==1 path)
@@ -494,10 +573,11 @@ __global__ __launch_bounds__(128, DIET ? 4 : 3) void decode_attn_mfma_kernel(
     const int* __restrict__ context_lens, // [seqs]
     const float scale, const int num_kv_heads, const int max_pages,
     const int num_splits, const int num_seqs, const int q_stride) {
+  static_assert(WS == 1 || ((WS == 2 || WS == 4) && !DIET), "WS is 1, 2, 4");
   const int kvh = blockIdx.x;
   const int wave = threadIdx.x >> 6;
-  const int seq = blockIdx.y * 2 + wave;
-  const int split = blockIdx.z;
+  const int seq = WS == 1 ? blockIdx.y * 2 + wave : blockIdx.y;
+  const int split = WS == 1 ? blockIdx.z : blockIdx.z * WS + wave;
   const int lane = threadIdx.x & 63;
   const int gl = lane & 15;
   const int gslice = lane >> 4;
@@ -508,12 +588,17 @@ __global__ __launch_bounds__(128, DIET ? 4 : 3) void decode_attn_mfma_kernel(
   // write-after-read needs no fence) — halving LDS doubles resident
   // waves.  V is fully rewritten every pair (tail pages clamp to real
   // pages and are masked through P=0), so no zero-init is needed.
-  __shared__ __hip_bfloat16 kv_all[2][32 * DM_KP];  // K panel / V tr image
-  __shared__ __hip_bfloat16 p_lds_all[2][16 * DM_PP];
+  constexpr int NW = WS == 1 ? 2 : WS;              // waves per workgroup
+  __shared__ __hip_bfloat16 kv_all[NW][32 * DM_KP];  // K panel / V tr image
+  __shared__ __hip_bfloat16 p_lds_all[NW][16 * DM_PP];
   __hip_bfloat16* k_lds = kv_all[wave];
   __hip_bfloat16* v_img = kv_all[wave];
   __hip_bfloat16* p_lds = p_lds_all[wave];
-  if (seq >= num_seqs) return;
+  // WS > 1: seq is uniform in the workgroup and every wave reaches the
+  // epilogue's barrier
+  if constexpr (WS == 1) {
+    if (seq >= num_seqs) return;
+  }
   const SplitRange sr = split_range(context_lens[seq], split, num_splits);
 
   // DIET: fragments reload per pair (L1)
@@ -568,9 +653,16 @@ __global__ __launch_bounds__(128, DIET ? 4 : 3) void decode_attn_mfma_kernel(
     }
   }
 
-  store_pair_output<QPG>(partial_o, partial_ml, out, acc_o, m, l, seq,
-                         num_seqs, split, num_splits, kvh, num_kv_heads, gl,
-                         gslice);
+  // num_splits == WS (gridDim.z == 1, the only way the launcher starts a
+  // WS > 1 kernel): merge in LDS.  Any other multiple of WS would write
+  // partials like WS = 1; see the note on that branch at merge_in_workgroup.
+  if (WS == 1 || num_splits != WS)
+    store_pair_output<QPG>(partial_o, partial_ml, out, acc_o, m, l, seq,
+                           num_seqs, split, num_splits, kvh, num_kv_heads, gl,
+                           gslice);
+  else
+    merge_in_workgroup<QPG, WS>(out, &kv_all[0][0], acc_o, m, l, wave, seq,
+                                kvh, num_kv_heads, gl, gslice);
 }
 
 // ---------------------------------------------------------------------------
@@ -751,8 +843,9 @@ DEV_INLINE void fp8x16_to_bf16(const uint4& b, uint4& lo, uint4& hi) {
     DQ_WRITE1(R##3, AT, 48);                                                \
   } while (0)
 
-template <int QPG>
-__global__ __launch_bounds__(128, 3) void decode_attn_mfma_fp8_kernel(
+template <int QPG, int WS = 1>
+__global__ __launch_bounds__(WS == 1 ? 128 : 64 * WS, 3)
+void decode_attn_mfma_fp8_kernel(
     float* __restrict__ partial_o,        // [splits, seqs, QH, D]
     float* __restrict__ partial_ml,       // [splits, seqs, QH, 2]
     __hip_bfloat16* __restrict__ out,     // [seqs, QH, D] (splits==1 path)
@@ -765,21 +858,25 @@ __global__ __launch_bounds__(128, 3) void decode_attn_mfma_fp8_kernel(
     const float v_scale,                  // 2^ev
     const int num_kv_heads, const int max_pages,
     const int num_splits, const int num_seqs, const int q_stride) {
+  static_assert(WS == 1 || ((WS == 2 || WS == 4)), "WS is 1, 2, 4");
   const int kvh = blockIdx.x;
   const int wave = threadIdx.x >> 6;
-  const int seq = blockIdx.y * 2 + wave;
-  const int split = blockIdx.z;
+  const int seq = WS == 1 ? blockIdx.y * 2 + wave : blockIdx.y;
+  const int split = WS == 1 ? blockIdx.z : blockIdx.z * WS + wave;
   const int lane = threadIdx.x & 63;
   const int gl = lane & 15;
   const int gslice = lane >> 4;
 
   // per-wave LDS, K panel and V image sharing one buffer (see variant 4)
-  __shared__ __hip_bfloat16 kv_all[2][32 * DM_KP];
-  __shared__ __hip_bfloat16 p_lds_all[2][16 * DM_PP];
+  constexpr int NW = WS == 1 ? 2 : WS;
+  __shared__ __hip_bfloat16 kv_all[NW][32 * DM_KP];
+  __shared__ __hip_bfloat16 p_lds_all[NW][16 * DM_PP];
   __hip_bfloat16* k_lds = kv_all[wave];
   __hip_bfloat16* v_img = kv_all[wave];
   __hip_bfloat16* p_lds = p_lds_all[wave];
-  if (seq >= num_seqs) return;
+  if constexpr (WS == 1) {
+    if (seq >= num_seqs) return;
+  }
   const SplitRange sr = split_range(context_lens[seq], split, num_splits);
 
   bf8 qa[4];
@@ -826,9 +923,16 @@ __global__ __launch_bounds__(128, 3) void decode_attn_mfma_fp8_kernel(
 #pragma unroll
     for (int r = 0; r < 4; ++r) acc_o[dt][r] *= v_scale;
 
-  store_pair_output<QPG>(partial_o, partial_ml, out, acc_o, m, l, seq,
-                         num_seqs, split, num_splits, kvh, num_kv_heads, gl,
-                         gslice);
+  // num_splits == WS (gridDim.z == 1, the only way the launcher starts a
+  // WS > 1 kernel): merge in LDS.  Any other multiple of WS would write
+  // partials like WS = 1; see the note on that branch at merge_in_workgroup.
+  if (WS == 1 || num_splits != WS)
+    store_pair_output<QPG>(partial_o, partial_ml, out, acc_o, m, l, seq,
+                           num_seqs, split, num_splits, kvh, num_kv_heads, gl,
+                           gslice);
+  else
+    merge_in_workgroup<QPG, WS>(out, &kv_all[0][0], acc_o, m, l, wave, seq,
+                                kvh, num_kv_heads, gl, gslice);
 }
 
 #undef DQ_REGS
@@ -849,21 +953,11 @@ __global__ void decode_combine_kernel(
     const int num_splits, const int num_q_heads) {
   const int seq = blockIdx.x, qh = blockIdx.y, d = threadIdx.x;
   const int seqs = gridDim.x;
-  float m_star = NEG_INF;
-  for (int s = 0; s < num_splits; ++s)
-    m_star = fmaxf(m_star,
-                   partial_ml[(((size_t)s * seqs + seq) * num_q_heads + qh) * 2]);
-  float o = 0.f, lsum = 0.f;
-  for (int s = 0; s < num_splits; ++s) {
-    const float* ml =
-        partial_ml + (((size_t)s * seqs + seq) * num_q_heads + qh) * 2;
-    const float f = __expf(ml[0] - m_star);
-    o += partial_o[(((size_t)s * seqs + seq) * num_q_heads + qh) * HEAD_DIM +
-                   d] * f;
-    lsum += ml[1] * f;
-  }
-  out[((size_t)seq * num_q_heads + qh) * HEAD_DIM + d] =
-      f2bf(lsum > 0.f ? o / lsum : 0.f);
+  auto row = [&](int s) { return ((size_t)s * seqs + seq) * num_q_heads + qh; };
+  out[((size_t)seq * num_q_heads + qh) * HEAD_DIM + d] = merge_splits(
+      num_splits, [&](int s) { return partial_ml[row(s) * 2]; },
+      [&](int s) { return partial_ml[row(s) * 2 + 1]; },
+      [&](int s) { return partial_o[row(s) * HEAD_DIM + d]; });
 }
 
 // Every decode kernel takes 8 pointers, the scale and 5 ints; only the
@@ -887,18 +981,64 @@ DecodeKernel decode_kernel(int variant) {
   }
 }
 
+// Variant 4 with the splits as the waves of one workgroup (WS = 2, 4)
+template <int QPG>
+DecodeKernel decode_wg_kernel(int ws) {
+  return ws == 2   ? decode_attn_mfma_kernel<QPG, 0, 2>
+         : ws == 4 ? decode_attn_mfma_kernel<QPG, 0, 4>
+                   : nullptr;
+}
+
+typedef void (*Fp8Kernel)(float*, float*, __hip_bfloat16*,
+                          const __hip_bfloat16*, const uint8_t*,
+                          const uint8_t*, const int*, const int*, float,
+                          float, int, int, int, int, int);
+
+template <int QPG>
+Fp8Kernel decode_fp8_kernel(int ws) {
+  return ws == 1   ? decode_attn_mfma_fp8_kernel<QPG, 1>
+         : ws == 2 ? decode_attn_mfma_fp8_kernel<QPG, 2>
+         : ws == 4 ? decode_attn_mfma_fp8_kernel<QPG, 4>
+                   : nullptr;
+}
+
 }  // namespace
 
 extern "C" {
 
+// in_wg: the splits are merged inside the workgroup (variant 4, 16-token
+// pages, num_splits 2 or 4; validated host-side) and the partials are unused.
 void launch_decode_attention(void* out, void* partial_o, void* partial_ml,
                              const void* q, const void* key_cache,
                              const void* val_cache, const void* block_tables,
                              const void* context_lens, float scale,
                              int num_seqs, int num_q_heads, int num_kv_heads,
                              int page_size, int max_pages, int num_splits,
-                             int variant, int q_stride, hipStream_t stream) {
+                             int variant, int q_stride, int in_wg,
+                             hipStream_t stream) {
   const int qpg = num_q_heads / num_kv_heads;
+  if (in_wg) {
+    // ws == num_splits and gridDim.z == 1 always: the kernels' partial-
+    // writing branch (num_splits != WS) is never started, so the partial
+    // pointers may be null; any other split count has no kernel here
+    const int ws = num_splits;
+    if (ws != 2 && ws != 4) return;   // a WS kernel only ever runs WS splits
+    const DecodeKernel wg = qpg == 1   ? decode_wg_kernel<1>(ws)
+                            : qpg == 2 ? decode_wg_kernel<2>(ws)
+                            : qpg == 4 ? decode_wg_kernel<4>(ws)
+                            : qpg == 8 ? decode_wg_kernel<8>(ws)
+                                       : nullptr;
+    if (wg == nullptr) return;     // validated host-side
+    hipLaunchKernelGGL(wg, dim3(num_kv_heads, num_seqs, 1), dim3(64 * ws), 0,
+                       stream, (float*)nullptr, (float*)nullptr,
+                       (__hip_bfloat16*)out, (const __hip_bfloat16*)q,
+                       (const __hip_bfloat16*)key_cache,
+                       (const __hip_bfloat16*)val_cache,
+                       (const int*)block_tables, (const int*)context_lens,
+                       scale, num_kv_heads, max_pages, num_splits, num_seqs,
+                       q_stride);
+    return;
+  }
   // the MFMA kernels need 16-token pages; otherwise, and for out-of-range
   // variants, fall back to the dot2 kernel (variant 1)
   const bool mfma = variant >= 4 && variant <= 6 && page_size == 16;
@@ -941,27 +1081,28 @@ void launch_decode_attention_fp8(void* out, void* partial_o, void* partial_ml,
                                  const void* context_lens, float k_scale,
                                  float v_scale, int num_seqs, int num_q_heads,
                                  int num_kv_heads, int max_pages,
-                                 int num_splits, int q_stride,
+                                 int num_splits, int q_stride, int in_wg,
                                  hipStream_t stream) {
-  typedef void (*Fp8Kernel)(float*, float*, __hip_bfloat16*,
-                            const __hip_bfloat16*, const uint8_t*,
-                            const uint8_t*, const int*, const int*, float,
-                            float, int, int, int, int, int);
   const int qpg = num_q_heads / num_kv_heads;
-  const Fp8Kernel kernel = qpg == 1   ? decode_attn_mfma_fp8_kernel<1>
-                           : qpg == 2 ? decode_attn_mfma_fp8_kernel<2>
-                           : qpg == 4 ? decode_attn_mfma_fp8_kernel<4>
-                           : qpg == 8 ? decode_attn_mfma_fp8_kernel<8>
+  const int ws = in_wg ? num_splits : 1;
+  // a WS kernel only ever runs WS splits (its partial pointers are null)
+  if (in_wg && ws != 2 && ws != 4) return;
+  const Fp8Kernel kernel = qpg == 1   ? decode_fp8_kernel<1>(ws)
+                           : qpg == 2 ? decode_fp8_kernel<2>(ws)
+                           : qpg == 4 ? decode_fp8_kernel<4>(ws)
+                           : qpg == 8 ? decode_fp8_kernel<8>(ws)
                                       : nullptr;
   if (kernel == nullptr) return;   // validated host-side
-  const dim3 grid(num_kv_heads, (num_seqs + 1) / 2, num_splits);
-  hipLaunchKernelGGL(kernel, grid, dim3(128), 0, stream, (float*)partial_o,
+  const dim3 grid(num_kv_heads, ws == 1 ? (num_seqs + 1) / 2 : num_seqs,
+                  ws == 1 ? num_splits : 1);
+  hipLaunchKernelGGL(kernel, grid, dim3(ws == 1 ? 128 : 64 * ws), 0, stream,
+                     (float*)partial_o,
                      (float*)partial_ml, (__hip_bfloat16*)out,
                      (const __hip_bfloat16*)q, (const uint8_t*)key_cache,
                      (const uint8_t*)val_cache, (const int*)block_tables,
                      (const int*)context_lens, k_scale, v_scale, num_kv_heads,
                      max_pages, num_splits, num_seqs, q_stride);
-  if (num_splits > 1) {
+  if (ws == 1 && num_splits > 1) {
     dim3 cgrid(num_seqs, num_q_heads), cblock(HEAD_DIM);
     hipLaunchKernelGGL(decode_combine_kernel, cgrid, cblock, 0, stream,
                        (__hip_bfloat16*)out, (const float*)partial_o,

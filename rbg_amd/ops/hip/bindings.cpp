@@ -20,7 +20,7 @@ void launch_rope_store_kv(void*, void*, const void*, void*, void*,
                           int, int, int, int, int, hipStream_t);
 void launch_decode_attention(void*, void*, void*, const void*, const void*,
                              const void*, const void*, const void*, float,
-                             int, int, int, int, int, int, int, int,
+                             int, int, int, int, int, int, int, int, int,
                              hipStream_t);
 void launch_prefill_attention(void*, const void*, const void*, const void*,
                               const void*, const void*, float, int, int, int,
@@ -49,7 +49,7 @@ void launch_kv_gather_dequant(void*, const void*, const void*, long, int, int,
                               int, float, hipStream_t);
 void launch_decode_attention_fp8(void*, void*, void*, const void*, const void*,
                                  const void*, const void*, const void*, float,
-                                 float, int, int, int, int, int, int,
+                                 float, int, int, int, int, int, int, int,
                                  hipStream_t);
 long xgmi_allreduce_signal_bytes();
 long xgmi_allreduce_error_offset();
@@ -205,11 +205,31 @@ void rope_store_kv(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                        current_stream());
 }
 
+// How the partials of num_splits > 1 are merged.  combine 0: inside the
+// workgroup where a kernel for it exists (the page-pair MFMA kernels at 2 or
+// 4 splits), else by decode_combine_kernel; 1: always the separate kernel;
+// 2: inside the workgroup, raising where that is not possible.
+bool pick_in_wg_combine(int64_t combine, int64_t num_splits, bool mfma_pair,
+                        const char* what) {
+  TORCH_CHECK(combine >= 0 && combine <= 2,
+              "combine must be 0 (auto), 1 (kernel) or 2 (in-workgroup)");
+  const bool can = mfma_pair && (num_splits == 2 || num_splits == 4);
+  TORCH_CHECK(combine != 2 || can, "combine = 2 needs ", what,
+              ", a page size of 16 and 2 or 4 splits");
+  const bool in_wg = combine != 1 && can;
+  // the in-workgroup kernels run exactly WS = num_splits splits and get no
+  // partial buffers: never hand them another count
+  TORCH_CHECK(!in_wg || num_splits == 2 || num_splits == 4,
+              "in-workgroup combine with ", num_splits, " splits");
+  return in_wg;
+}
+
 torch::Tensor decode_attention(torch::Tensor q, torch::Tensor key_cache,
                                torch::Tensor value_cache,
                                torch::Tensor block_tables,
                                torch::Tensor context_lens, double scale,
-                               int64_t num_splits, int64_t variant) {
+                               int64_t num_splits, int64_t variant,
+                               int64_t combine = 0) {
   // q may be a slice of the fused QKV projection: 3-D bf16 with
   // contiguous (head, dim) rows and an arbitrary token stride
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16 &&
@@ -235,12 +255,14 @@ torch::Tensor decode_attention(torch::Tensor q, torch::Tensor key_cache,
   TORCH_CHECK(context_lens.dim() == 1 && context_lens.size(0) == num_seqs,
               "context_lens must be [num_seqs]");
   TORCH_CHECK(num_splits >= 1, "num_splits must be >= 1");
+  const bool in_wg = pick_in_wg_combine(
+      combine, num_splits, variant == 4 && page_size == 16, "variant 4");
   const int max_pages = block_tables.size(1);
   auto out = torch::empty({num_seqs, num_q_heads, head_dim}, q.options());
   if (num_seqs == 0) return out;
   torch::Tensor partial_o, partial_ml;
   void *po = nullptr, *pml = nullptr;
-  if (num_splits > 1) {
+  if (num_splits > 1 && !in_wg) {
     auto opts = q.options().dtype(torch::kFloat32);
     partial_o = torch::empty({num_splits, num_seqs, num_q_heads, head_dim}, opts);
     partial_ml = torch::empty({num_splits, num_seqs, num_q_heads, 2}, opts);
@@ -252,7 +274,7 @@ torch::Tensor decode_attention(torch::Tensor q, torch::Tensor key_cache,
                           block_tables.data_ptr(), context_lens.data_ptr(),
                           (float)scale, num_seqs, num_q_heads, num_kv_heads,
                           page_size, max_pages, (int)num_splits, (int)variant,
-                          (int)q.stride(0), current_stream());
+                          (int)q.stride(0), in_wg, current_stream());
   return out;
 }
 
@@ -362,7 +384,8 @@ torch::Tensor decode_attention_fp8(torch::Tensor q, torch::Tensor key_cache,
                                    torch::Tensor block_tables,
                                    torch::Tensor context_lens, double scale,
                                    int64_t num_splits, int64_t k_scale_log2,
-                                   int64_t v_scale_log2) {
+                                   int64_t v_scale_log2,
+                                   int64_t combine = 0) {
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16 &&
               q.dim() == 3 && q.stride(2) == 1 &&
               q.stride(1) == q.size(2), "q must be [T, QH, D] row-sliced");
@@ -387,12 +410,14 @@ torch::Tensor decode_attention_fp8(torch::Tensor q, torch::Tensor key_cache,
   TORCH_CHECK(context_lens.dim() == 1 && context_lens.size(0) == num_seqs,
               "context_lens must be [num_seqs]");
   TORCH_CHECK(num_splits >= 1, "num_splits must be >= 1");
+  const bool in_wg =
+      pick_in_wg_combine(combine, num_splits, true, "the fp8 kernel");
   const int max_pages = block_tables.size(1);
   auto out = torch::empty({num_seqs, num_q_heads, 128}, q.options());
   if (num_seqs == 0) return out;
   torch::Tensor partial_o, partial_ml;
   void *po = nullptr, *pml = nullptr;
-  if (num_splits > 1) {
+  if (num_splits > 1 && !in_wg) {
     auto opts = q.options().dtype(torch::kFloat32);
     partial_o = torch::empty({num_splits, num_seqs, num_q_heads, 128}, opts);
     partial_ml = torch::empty({num_splits, num_seqs, num_q_heads, 2}, opts);
@@ -406,7 +431,7 @@ torch::Tensor decode_attention_fp8(torch::Tensor q, torch::Tensor key_cache,
                               context_lens.data_ptr(), (float)scale * k_scale,
                               v_scale, num_seqs, num_q_heads, num_kv_heads,
                               max_pages, (int)num_splits, (int)q.stride(0),
-                              current_stream());
+                              in_wg, current_stream());
   return out;
 }
 
@@ -807,13 +832,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_add_rmsnorm", &fused_add_rmsnorm, "x,residual += ; rmsnorm");
   m.def("silu_mul", &silu_mul, "silu(gate)*up");
   m.def("rope_store_kv", &rope_store_kv, "RoPE + paged KV write");
-  m.def("decode_attention", &decode_attention, "paged flash-decode");
+  m.def("decode_attention", &decode_attention, "paged flash-decode",
+        py::arg("q"), py::arg("key_cache"), py::arg("value_cache"),
+        py::arg("block_tables"), py::arg("context_lens"), py::arg("scale"),
+        py::arg("num_splits"), py::arg("variant"), py::arg("combine") = 0);
   m.def("rope_store_kv_fp8", &rope_store_kv_fp8,
         "RoPE + quantising (e4m3) paged KV write");
   m.def("kv_gather_dequant", &kv_gather_dequant,
         "gather e4m3 cache rows by slot -> bf16 [Tkv, KVH, D]");
   m.def("decode_attention_fp8", &decode_attention_fp8,
-        "paged flash-decode over an e4m3 cache (page-pair MFMA)");
+        "paged flash-decode over an e4m3 cache (page-pair MFMA)",
+        py::arg("q"), py::arg("key_cache"), py::arg("value_cache"),
+        py::arg("block_tables"), py::arg("context_lens"), py::arg("scale"),
+        py::arg("num_splits"), py::arg("k_scale_log2"),
+        py::arg("v_scale_log2"), py::arg("combine") = 0);
   m.def("prefill_attention", &prefill_attention, "varlen causal flash prefill");
   m.def("mfma_probe", &mfma_probe, "MFMA layout probe");
   m.def("mfma_probe32", &mfma_probe32, "32x32x16 MFMA layout probe");
