@@ -151,24 +151,20 @@ def rope_store_kv(q, k, v, key_cache, value_cache, cos_sin, positions,
     """RoPE on q, k in place, then the paged KV write.  An e4m3 cache
     receives sat_rne_e4m3fn(x * 2^-e) of the bf16 value a bf16 cache would
     have received; the exponents are ignored for a bf16 cache."""
-    if _is_fp8_pair(key_cache, value_cache):
+    fp8 = _is_fp8_pair(key_cache, value_cache)
+    scales = ()
+    if fp8:
         check_kv_scale_log2(k_scale_log2, "kv_k_scale_log2")
         check_kv_scale_log2(v_scale_log2, "kv_v_scale_log2")
-        if _on_gpu(q):
-            _require_hip().rope_store_kv_fp8(
-                q, k, v, key_cache, value_cache, cos_sin, positions,
-                slot_mapping, k_scale_log2, v_scale_log2)
-            return
-        reference.rope_store_kv(q, k, v, key_cache, value_cache, cos_sin,
-                                positions, slot_mapping, k_scale_log2,
-                                v_scale_log2)
-        return
-    if _on_gpu(q):
-        _require_hip().rope_store_kv(q, k, v, key_cache, value_cache,
-                                     cos_sin, positions, slot_mapping)
-        return
-    reference.rope_store_kv(q, k, v, key_cache, value_cache, cos_sin,
-                            positions, slot_mapping)
+        scales = (k_scale_log2, v_scale_log2)
+    args = (q, k, v, key_cache, value_cache, cos_sin, positions,
+            slot_mapping) + scales
+    if not _on_gpu(q):
+        reference.rope_store_kv(*args)
+    elif fp8:
+        _require_hip().rope_store_kv_fp8(*args)
+    else:
+        _require_hip().rope_store_kv(*args)
 
 
 def kv_gather_dequant(cache, slots, scale_log2: int = 0) -> torch.Tensor:
@@ -220,7 +216,9 @@ def decode_attention(q, key_cache, value_cache, block_tables, context_lens,
     workgroup and neither partials nor a second launch exist; else by
     decode_combine_kernel), 1 forces the separate kernel, 2 the in-workgroup
     merge (raising where no kernel has it).  Both give the same bits."""
-    if _is_fp8_pair(key_cache, value_cache):
+    fp8 = _is_fp8_pair(key_cache, value_cache)
+    scales = ()
+    if fp8:
         # one kernel reads an e4m3 cache: the page-pair MFMA one (variant 4)
         if variant not in (-1, 4):
             raise ValueError("an fp8 KV cache has no decode variant %d: only "
@@ -231,30 +229,21 @@ def decode_attention(q, key_cache, value_cache, block_tables, context_lens,
             raise ValueError("fp8 decode needs page size 16 and head_dim 128, "
                              "got %d and %d" % (key_cache.shape[2],
                                                 key_cache.shape[3]))
-        if _on_gpu(q):
-            if num_splits <= 0:
-                max_ctx = (int(context_lens.max().item())
-                           if context_lens.numel() else 1)
-                num_splits = pick_decode_splits(q.shape[0],
-                                                key_cache.shape[1], max_ctx, 4)
-            return _require_hip().decode_attention_fp8(
-                q, key_cache, value_cache, block_tables, context_lens, scale,
-                num_splits, k_scale_log2, v_scale_log2, combine)
-        return reference.decode_attention(
-            q, key_cache, value_cache, block_tables, context_lens, scale,
-            k_scale_log2, v_scale_log2)
-    if _on_gpu(q):
-        if num_splits <= 0:
-            max_ctx = int(context_lens.max().item()) if context_lens.numel() else 1
-            num_splits = pick_decode_splits(q.shape[0], key_cache.shape[1],
-                                            max_ctx)
-        if variant < 0:
-            variant = DECODE_VARIANT
-        return _require_hip().decode_attention(
-            q, key_cache, value_cache, block_tables, context_lens, scale,
-            num_splits, variant, combine)
-    return reference.decode_attention(q, key_cache, value_cache, block_tables,
-                                      context_lens, scale)
+        scales = (k_scale_log2, v_scale_log2)
+    args = (q, key_cache, value_cache, block_tables, context_lens, scale)
+    if not _on_gpu(q):
+        return reference.decode_attention(*args, *scales)
+    if num_splits <= 0:
+        max_ctx = int(context_lens.max().item()) if context_lens.numel() else 1
+        # a bf16 cache gets the default variant's split policy whatever
+        # `variant` says
+        num_splits = pick_decode_splits(q.shape[0], key_cache.shape[1],
+                                        max_ctx, 4 if fp8 else -1)
+    if fp8:
+        return _require_hip().decode_attention_fp8(*args, num_splits, *scales,
+                                                   combine)
+    return _require_hip().decode_attention(
+        *args, num_splits, DECODE_VARIANT if variant < 0 else variant, combine)
 
 
 def prefill_attention(q, k, v, cu_seqlens, scale: float,

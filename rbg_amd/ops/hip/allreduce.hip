@@ -36,6 +36,7 @@
 // engines' NCCL (SURVEY §2.2 TP row; §5 "prefer direct reduce-scatter/
 // all-gather over per-link-bound ring" note).
 #include "common.h"
+#include "launch.h"
 
 #define AR_MAX_WORLD 8
 #define AR_BLOCKS 64
@@ -133,9 +134,9 @@ __global__ __launch_bounds__(AR_THREADS) void xgmi_allreduce_kernel(
 
 extern "C" {
 
-void launch_xgmi_allreduce(void* out, const void* in, void** sig_ptrs,
-                           void** data_ptrs, int world, int rank, long n,
-                           hipStream_t stream) {
+hipError_t launch_xgmi_allreduce(void* out, const void* in, void** sig_ptrs,
+                                 void** data_ptrs, int world, int rank, long n,
+                                 hipStream_t stream) {
   RankPtrs ptrs;
   for (int i = 0; i < AR_MAX_WORLD; ++i) {
     ptrs.sig[i] = (Signals*)(i < world ? sig_ptrs[i] : nullptr);
@@ -155,10 +156,10 @@ void launch_xgmi_allreduce(void* out, const void* in, void** sig_ptrs,
     case 6: AR_LAUNCH(6); break;
     case 7: AR_LAUNCH(7); break;
     case 8: AR_LAUNCH(8); break;
-    default: break;
+    default: return hipErrorInvalidValue;
   }
 #undef AR_LAUNCH
-  HIP_KERNEL_CHECK();
+  return hipGetLastError();
 }
 
 long xgmi_allreduce_signal_bytes() { return (long)sizeof(Signals); }

@@ -23,6 +23,7 @@
 // Capability analog: the decode-side paged attention of the engines the
 // reference orchestrates (SURVEY §2.3 decode engine row).
 #include "attn_mfma.h"
+#include "launch.h"
 
 namespace {
 
@@ -960,8 +961,9 @@ __global__ void decode_combine_kernel(
       [&](int s) { return partial_o[row(s) * HEAD_DIM + d]; });
 }
 
-// Every decode kernel takes 8 pointers, the scale and 5 ints; only the
-// meaning of the middle ints differs (see launch_decode_attention).
+// Every bf16 decode kernel takes 8 pointers, the scale and 5 ints; the
+// middle three ints differ between the dot2 and the MFMA kernels (Dot2Ints,
+// MfmaInts below).
 typedef void (*DecodeKernel)(float*, float*, __hip_bfloat16*,
                              const __hip_bfloat16*, const __hip_bfloat16*,
                              const __hip_bfloat16*, const int*, const int*,
@@ -1002,112 +1004,98 @@ Fp8Kernel decode_fp8_kernel(int ws) {
                    : nullptr;
 }
 
+// The kernel for a GQA group size: F<QPG>(arg) for the instantiated groups
+// 1, 2, 4 and 8, null for every other.
+#define FOR_QPG(F, qpg, arg)       \
+  ((qpg) == 1   ? F<1>(arg)        \
+   : (qpg) == 2 ? F<2>(arg)        \
+   : (qpg) == 4 ? F<4>(arg)        \
+   : (qpg) == 8 ? F<8>(arg)        \
+                : nullptr)
+
+// The ints between num_kv_heads and q_stride, in kernel parameter order.
+struct TailInts {
+  int a, b, c;
+};
+TailInts dot2_ints(const DecodeLaunch& d, int page_size) {
+  return {page_size, d.max_pages, d.num_splits};
+}
+TailInts mfma_ints(const DecodeLaunch& d) {
+  return {d.max_pages, d.num_splits, d.num_seqs};
+}
+
+hipError_t launch_combine(const DecodeLaunch& d, hipStream_t stream) {
+  dim3 cgrid(d.num_seqs, d.num_q_heads), cblock(HEAD_DIM);
+  hipLaunchKernelGGL(decode_combine_kernel, cgrid, cblock, 0, stream,
+                     (__hip_bfloat16*)d.out, (const float*)d.partial_o,
+                     (const float*)d.partial_ml, d.num_splits, d.num_q_heads);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 extern "C" {
 
-// in_wg: the splits are merged inside the workgroup (variant 4, 16-token
-// pages, num_splits 2 or 4; validated host-side) and the partials are unused.
-void launch_decode_attention(void* out, void* partial_o, void* partial_ml,
-                             const void* q, const void* key_cache,
-                             const void* val_cache, const void* block_tables,
-                             const void* context_lens, float scale,
-                             int num_seqs, int num_q_heads, int num_kv_heads,
-                             int page_size, int max_pages, int num_splits,
-                             int variant, int q_stride, int in_wg,
-                             hipStream_t stream) {
-  const int qpg = num_q_heads / num_kv_heads;
-  if (in_wg) {
-    // ws == num_splits and gridDim.z == 1 always: the kernels' partial-
-    // writing branch (num_splits != WS) is never started, so the partial
-    // pointers may be null; any other split count has no kernel here
-    const int ws = num_splits;
-    if (ws != 2 && ws != 4) return;   // a WS kernel only ever runs WS splits
-    const DecodeKernel wg = qpg == 1   ? decode_wg_kernel<1>(ws)
-                            : qpg == 2 ? decode_wg_kernel<2>(ws)
-                            : qpg == 4 ? decode_wg_kernel<4>(ws)
-                            : qpg == 8 ? decode_wg_kernel<8>(ws)
-                                       : nullptr;
-    if (wg == nullptr) return;     // validated host-side
-    hipLaunchKernelGGL(wg, dim3(num_kv_heads, num_seqs, 1), dim3(64 * ws), 0,
-                       stream, (float*)nullptr, (float*)nullptr,
-                       (__hip_bfloat16*)out, (const __hip_bfloat16*)q,
-                       (const __hip_bfloat16*)key_cache,
-                       (const __hip_bfloat16*)val_cache,
-                       (const int*)block_tables, (const int*)context_lens,
-                       scale, num_kv_heads, max_pages, num_splits, num_seqs,
-                       q_stride);
-    return;
-  }
-  // the MFMA kernels need 16-token pages; otherwise, and for out-of-range
-  // variants, fall back to the dot2 kernel (variant 1)
+hipError_t launch_decode_attention(const DecodeLaunch& d, int page_size,
+                                   int variant, hipStream_t stream) {
+  if (d.num_kv_heads < 1) return hipErrorInvalidValue;
+  const int qpg = d.num_q_heads / d.num_kv_heads;
+  // the MFMA kernels (variants 4-6) need 16-token pages: at any other page
+  // size they are served by the dot2 kernel, variant 1
   const bool mfma = variant >= 4 && variant <= 6 && page_size == 16;
-  const int v = (mfma || (variant >= 0 && variant <= 3)) ? variant : 1;
-  const DecodeKernel kernel = qpg == 1   ? decode_kernel<1>(v)
-                              : qpg == 2 ? decode_kernel<2>(v)
-                              : qpg == 4 ? decode_kernel<4>(v)
-                              : qpg == 8 ? decode_kernel<8>(v)
-                                         : nullptr;
-  if (kernel == nullptr) return;   // validated host-side
+  const int v = variant >= 4 && variant <= 6 && !mfma ? 1 : variant;
+  // in the workgroup: WS == num_splits and gridDim.z == 1, so the kernels'
+  // partial-writing branch (num_splits != WS) never runs and gets no buffers
+  if (d.in_wg && !(variant == 4 && mfma)) return hipErrorInvalidValue;
+  if (!d.in_wg && d.num_splits > 1 && !(d.partial_o && d.partial_ml))
+    return hipErrorInvalidValue;
+  const int ws = d.in_wg ? d.num_splits : 1;
+  const DecodeKernel kernel = d.in_wg ? FOR_QPG(decode_wg_kernel, qpg, ws)
+                                      : FOR_QPG(decode_kernel, qpg, v);
+  if (kernel == nullptr) return hipErrorInvalidValue;
   // variants 4/5 pack two sequences (one per wave) into a workgroup
-  const int seq_blocks = (v == 4 || v == 5) ? (num_seqs + 1) / 2 : num_seqs;
-  const dim3 grid(num_kv_heads, seq_blocks, num_splits);
-  const dim3 block(mfma ? 128 : 256);
-  // int tail: dot2 (page_size, max_pages, num_splits),
-  //           MFMA (max_pages, num_splits, num_seqs)
-  hipLaunchKernelGGL(kernel, grid, block, 0, stream, (float*)partial_o,
-                     (float*)partial_ml, (__hip_bfloat16*)out,
-                     (const __hip_bfloat16*)q,
-                     (const __hip_bfloat16*)key_cache,
-                     (const __hip_bfloat16*)val_cache,
-                     (const int*)block_tables, (const int*)context_lens,
-                     scale, num_kv_heads, mfma ? max_pages : page_size,
-                     mfma ? num_splits : max_pages,
-                     mfma ? num_seqs : num_splits, q_stride);
-  if (num_splits > 1) {
-    dim3 cgrid(num_seqs, num_q_heads), cblock(HEAD_DIM);
-    hipLaunchKernelGGL(decode_combine_kernel, cgrid, cblock, 0, stream,
-                       (__hip_bfloat16*)out, (const float*)partial_o,
-                       (const float*)partial_ml, num_splits, num_q_heads);
-  }
+  const int seq_blocks =
+      !d.in_wg && (v == 4 || v == 5) ? (d.num_seqs + 1) / 2 : d.num_seqs;
+  const dim3 grid(d.num_kv_heads, seq_blocks, d.in_wg ? 1 : d.num_splits);
+  const dim3 block(d.in_wg ? 64 * ws : mfma ? 128 : 256);
+  const TailInts t = mfma ? mfma_ints(d) : dot2_ints(d, page_size);
+  hipLaunchKernelGGL(kernel, grid, block, 0, stream, (float*)d.partial_o,
+                     (float*)d.partial_ml, (__hip_bfloat16*)d.out,
+                     (const __hip_bfloat16*)d.q,
+                     (const __hip_bfloat16*)d.key_cache,
+                     (const __hip_bfloat16*)d.val_cache,
+                     (const int*)d.block_tables, (const int*)d.context_lens,
+                     d.scale, d.num_kv_heads, t.a, t.b, t.c, d.q_stride);
+  return !d.in_wg && d.num_splits > 1 ? launch_combine(d, stream)
+                                      : hipGetLastError();
 }
 
-// e4m3 caches with 16-token pages (validated host-side).  k_scale is the
-// softmax scale times 2^ek, v_scale is 2^ev.
-void launch_decode_attention_fp8(void* out, void* partial_o, void* partial_ml,
-                                 const void* q, const void* key_cache,
-                                 const void* val_cache,
-                                 const void* block_tables,
-                                 const void* context_lens, float k_scale,
-                                 float v_scale, int num_seqs, int num_q_heads,
-                                 int num_kv_heads, int max_pages,
-                                 int num_splits, int q_stride, int in_wg,
-                                 hipStream_t stream) {
-  const int qpg = num_q_heads / num_kv_heads;
-  const int ws = in_wg ? num_splits : 1;
+// e4m3 caches with 16-token pages.  d.scale is the softmax scale times 2^ek,
+// v_scale is 2^ev.
+hipError_t launch_decode_attention_fp8(const DecodeLaunch& d, float v_scale,
+                                       hipStream_t stream) {
+  if (d.num_kv_heads < 1) return hipErrorInvalidValue;
+  const int qpg = d.num_q_heads / d.num_kv_heads;
   // a WS kernel only ever runs WS splits (its partial pointers are null)
-  if (in_wg && ws != 2 && ws != 4) return;
-  const Fp8Kernel kernel = qpg == 1   ? decode_fp8_kernel<1>(ws)
-                           : qpg == 2 ? decode_fp8_kernel<2>(ws)
-                           : qpg == 4 ? decode_fp8_kernel<4>(ws)
-                           : qpg == 8 ? decode_fp8_kernel<8>(ws)
-                                      : nullptr;
-  if (kernel == nullptr) return;   // validated host-side
-  const dim3 grid(num_kv_heads, ws == 1 ? (num_seqs + 1) / 2 : num_seqs,
-                  ws == 1 ? num_splits : 1);
+  const int ws = d.in_wg ? d.num_splits : 1;
+  if (d.in_wg && ws != 2 && ws != 4) return hipErrorInvalidValue;
+  if (!d.in_wg && d.num_splits > 1 && !(d.partial_o && d.partial_ml))
+    return hipErrorInvalidValue;
+  const Fp8Kernel kernel = FOR_QPG(decode_fp8_kernel, qpg, ws);
+  if (kernel == nullptr) return hipErrorInvalidValue;
+  const dim3 grid(d.num_kv_heads,
+                  ws == 1 ? (d.num_seqs + 1) / 2 : d.num_seqs,
+                  ws == 1 ? d.num_splits : 1);
+  const TailInts t = mfma_ints(d);
   hipLaunchKernelGGL(kernel, grid, dim3(ws == 1 ? 128 : 64 * ws), 0, stream,
-                     (float*)partial_o,
-                     (float*)partial_ml, (__hip_bfloat16*)out,
-                     (const __hip_bfloat16*)q, (const uint8_t*)key_cache,
-                     (const uint8_t*)val_cache, (const int*)block_tables,
-                     (const int*)context_lens, k_scale, v_scale, num_kv_heads,
-                     max_pages, num_splits, num_seqs, q_stride);
-  if (ws == 1 && num_splits > 1) {
-    dim3 cgrid(num_seqs, num_q_heads), cblock(HEAD_DIM);
-    hipLaunchKernelGGL(decode_combine_kernel, cgrid, cblock, 0, stream,
-                       (__hip_bfloat16*)out, (const float*)partial_o,
-                       (const float*)partial_ml, num_splits, num_q_heads);
-  }
+                     (float*)d.partial_o, (float*)d.partial_ml,
+                     (__hip_bfloat16*)d.out, (const __hip_bfloat16*)d.q,
+                     (const uint8_t*)d.key_cache, (const uint8_t*)d.val_cache,
+                     (const int*)d.block_tables, (const int*)d.context_lens,
+                     d.scale, v_scale, d.num_kv_heads, t.a, t.b, t.c,
+                     d.q_stride);
+  return ws == 1 && d.num_splits > 1 ? launch_combine(d, stream)
+                                     : hipGetLastError();
 }
 
 }  // extern "C"

@@ -16,6 +16,7 @@
 // Capability analog: prefill attention of the engines the reference
 // orchestrates (SURVEY §2.3 prefill engine row).
 #include "attn_mfma.h"
+#include "launch.h"
 
 namespace {
 
@@ -511,19 +512,17 @@ PrefillKernel prefill_kernel(int swz) {
 
 extern "C" {
 
-void launch_prefill_attention(void* out, const void* q, const void* k,
-                              const void* v, const void* block_info,
-                              const void* seq_lens, float scale, int nblocks,
-                              int num_q_heads, int num_kv_heads, int swz,
-                              int q_stride, int kv_stride,
-                              hipStream_t stream) {
-  const dim3 grid(nblocks * num_q_heads);
-  const dim3 block((swz & 12) == 4 ? 512 : 256);   // only bit 2 alone: 8 waves
-  hipLaunchKernelGGL(prefill_kernel(swz), grid, block, 0, stream,
-                     (__hip_bfloat16*)out, (const __hip_bfloat16*)q,
-                     (const __hip_bfloat16*)k, (const __hip_bfloat16*)v,
-                     (const int*)block_info, (const int*)seq_lens, scale,
-                     num_q_heads, num_kv_heads, q_stride, kv_stride, nblocks);
+hipError_t launch_prefill_attention(const PrefillLaunch& a,
+                                    hipStream_t stream) {
+  const dim3 grid(a.nblocks * a.num_q_heads);
+  const dim3 block((a.swz & 12) == 4 ? 512 : 256);  // only bit 2 alone: 8 waves
+  hipLaunchKernelGGL(prefill_kernel(a.swz), grid, block, 0, stream,
+                     (__hip_bfloat16*)a.out, (const __hip_bfloat16*)a.q,
+                     (const __hip_bfloat16*)a.k, (const __hip_bfloat16*)a.v,
+                     (const int*)a.block_info, (const int*)a.seq_lens,
+                     a.scale, a.num_q_heads, a.num_kv_heads, a.q_stride,
+                     a.kv_stride, a.nblocks);
+  return hipGetLastError();
 }
 
 }  // extern "C"

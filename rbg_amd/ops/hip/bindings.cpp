@@ -1,5 +1,6 @@
 // PyTorch bindings for the rbg_amd CDNA4 HIP kernels.
-// Thin shape/dtype checks here; all math lives in the .hip translation units.
+// Shape/dtype checks here; all math lives in the .hip translation units,
+// whose launchers are declared in launch.h and nowhere else.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
@@ -10,51 +11,16 @@
 #include <cstring>
 #include <vector>
 
-extern "C" {
-void launch_rmsnorm(void*, void*, const void*, float, int, int, hipStream_t);
-void launch_fused_add_rmsnorm(void*, void*, const void*, float, int, int,
-                              hipStream_t);
-void launch_silu_mul(void*, const void*, int, int, hipStream_t);
-void launch_rope_store_kv(void*, void*, const void*, void*, void*,
-                          const void*, const void*, const void*, int, int,
-                          int, int, int, int, int, hipStream_t);
-void launch_decode_attention(void*, void*, void*, const void*, const void*,
-                             const void*, const void*, const void*, float,
-                             int, int, int, int, int, int, int, int, int,
-                             hipStream_t);
-void launch_prefill_attention(void*, const void*, const void*, const void*,
-                              const void*, const void*, float, int, int, int,
-                              int, int, int, hipStream_t);
-void launch_mfma_probe(void*, const void*, const void*, int, int, hipStream_t);
-void launch_mfma_probe32(void*, const void*, const void*, int, int, int,
-                         hipStream_t);
-void launch_skinny_gemm(void*, void*, const void*, const void*, int, int,
-                        int, int, hipStream_t);
-void launch_skinny_gemm_wide(void*, void*, const void*, const void*, int, int,
-                             int, int, hipStream_t);
-void launch_reduce_splits(void*, const void*, int, long, hipStream_t);
-void launch_fold_add_rmsnorm(void*, const void*, void*, const void*, float,
-                             int, int, int, hipStream_t);
-void launch_kv_peer_copy(void*, const void*, const void*, const void*, int,
-                         int, int, long, long, long, long, hipStream_t);
-void launch_xgmi_allreduce(void*, const void*, void**, void**, int, int,
-                           long, hipStream_t);
-void launch_sample(void*, void*, const void*, const void*, const void*,
-                   const void*, const void*, const void*, const void*, int,
-                   int, hipStream_t);
-void launch_rope_store_kv_fp8(void*, void*, const void*, void*, void*,
-                              const void*, const void*, const void*, int, int,
-                              int, int, int, int, float, float, hipStream_t);
-void launch_kv_gather_dequant(void*, const void*, const void*, long, int, int,
-                              int, float, hipStream_t);
-void launch_decode_attention_fp8(void*, void*, void*, const void*, const void*,
-                                 const void*, const void*, const void*, float,
-                                 float, int, int, int, int, int, int, int,
-                                 hipStream_t);
-long xgmi_allreduce_signal_bytes();
-long xgmi_allreduce_error_offset();
-long xgmi_allreduce_counter_offset();
-}
+#include "launch.h"
+
+// Calls a launcher of launch.h; an error it returns (no kernel for the
+// arguments, or a failed launch) raises RuntimeError.
+#define LAUNCH(launcher, ...)                                               \
+  do {                                                                      \
+    const hipError_t launch_err_ = launcher(__VA_ARGS__);                   \
+    TORCH_CHECK(launch_err_ == hipSuccess, #launcher, " failed: ",          \
+                hipGetErrorString(launch_err_));                            \
+  } while (0)
 
 namespace {
 
@@ -74,23 +40,59 @@ void check_i32_gpu(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
 
-// Paged KV pool views [pages, KVH, page_size, head_dim]: the kernels index
-// them as dense bf16 with a power-of-two page (shift/mask slot math) and
-// 16-byte row vectors, so anything else must raise instead of launching.
-void check_kv_caches(const torch::Tensor& key_cache,
-                     const torch::Tensor& value_cache) {
-  check_bf16_contig(key_cache, "key_cache");
-  check_bf16_contig(value_cache, "value_cache");
-  TORCH_CHECK(key_cache.dim() == 4,
-              "key_cache must be [pages, KVH, page_size, head_dim]");
-  TORCH_CHECK(value_cache.sizes() == key_cache.sizes(),
-              "key_cache/value_cache shape mismatch");
-  const int64_t page_size = key_cache.size(2);
+// bf16 on GPU, [T, H, D] with contiguous (H, D) rows, or [T, W] where
+// allow_2d; the TOKEN stride may be wider (a column slice of the fused QKV
+// buffer).
+void check_bf16_rowslice(const torch::Tensor& t, const char* name,
+                         bool allow_2d = false) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, name, " must be bf16");
+  if (allow_2d && t.dim() == 2) {
+    TORCH_CHECK(t.stride(1) == 1, name, " rows must be contiguous");
+  } else {
+    TORCH_CHECK(t.dim() == 3 && t.stride(2) == 1 &&
+                t.stride(1) == t.size(2), name,
+                " must be [T, H, D] with contiguous (H, D) rows");
+  }
+}
+
+// One paged KV pool view [pages, KVH, page_size, head_dim] of bf16 or e4m3:
+// the kernels index it densely with a power-of-two page (shift/mask slot
+// math) and 16-byte row vectors, so anything else must raise instead of
+// launching.
+void check_kv_cache(const torch::Tensor& t, const char* name,
+                    torch::ScalarType dtype) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.scalar_type() == dtype, name, " must be ",
+              dtype == torch::kBFloat16 ? "bf16" : "float8_e4m3fn");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.dim() == 4, name,
+              " must be [pages, KVH, page_size, head_dim]");
+  const int64_t page_size = t.size(2);
   TORCH_CHECK(page_size > 0 && (page_size & (page_size - 1)) == 0,
               "page_size must be a power of two");
-  TORCH_CHECK(key_cache.size(1) > 0, "cache needs at least one KV head");
-  TORCH_CHECK(key_cache.size(3) > 0 && key_cache.size(3) % 8 == 0,
-              "cache head_dim must be a multiple of 8");
+  TORCH_CHECK(t.size(1) > 0, "cache needs at least one KV head");
+  if (dtype == torch::kBFloat16) {
+    TORCH_CHECK(t.size(3) > 0 && t.size(3) % 8 == 0,
+                "cache head_dim must be a multiple of 8");
+  } else {
+    TORCH_CHECK(t.size(3) == 128, "fp8 cache head_dim must be 128");
+  }
+  // slots and rows reach the kernels as int32.  (The bf16 kernels widen to
+  // size_t before they multiply, and 2^31 bf16 rows exceed the HBM anyway:
+  // for them the check is only there to be the same one.)
+  TORCH_CHECK(t.numel() / t.size(3) <= INT32_MAX, "cache has too many slots");
+}
+
+void check_kv_caches(const torch::Tensor& key_cache,
+                     const torch::Tensor& value_cache,
+                     torch::ScalarType dtype) {
+  check_kv_cache(key_cache, "key_cache", dtype);
+  check_kv_cache(value_cache, "value_cache", dtype);
+  TORCH_CHECK(value_cache.sizes() == key_cache.sizes(),
+              "key_cache/value_cache shape mismatch");
+  TORCH_CHECK(value_cache.device() == key_cache.device(),
+              "key_cache/value_cache device mismatch");
 }
 
 // Shared by both norms: the kernels read weight[0 .. hidden) as 16-byte
@@ -112,8 +114,8 @@ torch::Tensor rmsnorm(torch::Tensor x, torch::Tensor weight, double eps) {
   const int tokens = x.numel() / hidden;
   auto out = torch::empty_like(x);
   if (tokens == 0) return out;
-  launch_rmsnorm(out.data_ptr(), x.data_ptr(), weight.data_ptr(), (float)eps,
-                 tokens, hidden, current_stream());
+  LAUNCH(launch_rmsnorm, out.data_ptr(), x.data_ptr(), weight.data_ptr(),
+         (float)eps, tokens, hidden, current_stream());
   return out;
 }
 
@@ -125,9 +127,8 @@ void fused_add_rmsnorm(torch::Tensor x, torch::Tensor residual,
   TORCH_CHECK(residual.device() == x.device(), "x/residual device mismatch");
   const int tokens = x.numel() / hidden;
   if (tokens == 0) return;
-  launch_fused_add_rmsnorm(x.data_ptr(), residual.data_ptr(),
-                           weight.data_ptr(), (float)eps, tokens, hidden,
-                           current_stream());
+  LAUNCH(launch_fused_add_rmsnorm, x.data_ptr(), residual.data_ptr(),
+         weight.data_ptr(), (float)eps, tokens, hidden, current_stream());
 }
 
 torch::Tensor silu_mul(torch::Tensor x) {
@@ -143,66 +144,121 @@ torch::Tensor silu_mul(torch::Tensor x) {
   out_sizes.back() = inter;
   auto out = torch::empty(out_sizes, x.options());
   if (tokens == 0) return out;
-  launch_silu_mul(out.data_ptr(), x.data_ptr(), tokens, inter,
-                  current_stream());
+  LAUNCH(launch_silu_mul, out.data_ptr(), x.data_ptr(), tokens, inter,
+         current_stream());
   return out;
 }
 
-static void check_bf16_rowslice(const torch::Tensor& t, const char* name) {
-  // bf16 on GPU, [T, W] or [T, H, D], innermost dims contiguous; the
-  // TOKEN stride may be wider (a column slice of the fused QKV buffer)
-  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
-  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, name, " must be bf16");
-  if (t.dim() == 2) {
-    TORCH_CHECK(t.stride(1) == 1, name, " rows must be contiguous");
-  } else {
-    TORCH_CHECK(t.dim() == 3 && t.stride(2) == 1 &&
-                t.stride(1) == t.size(2), name,
-                " must be [T, H, D] with contiguous (H, D) rows");
-  }
+// Scales of the e4m3 cache are powers of two given as integer exponents.
+float check_scale_log2(int64_t e, const char* name) {
+  TORCH_CHECK(e >= -16 && e <= 16, name, " must be in [-16, 16], got ", e);
+  return std::ldexp(1.0f, (int)e);
+}
+
+// Everything rope_store_kv checks and passes on for either cache dtype; the
+// e4m3 binding adds its scales.
+RopeStoreLaunch rope_store_args(const torch::Tensor& q, const torch::Tensor& k,
+                                const torch::Tensor& v,
+                                const torch::Tensor& key_cache,
+                                const torch::Tensor& value_cache,
+                                torch::ScalarType cache_dtype,
+                                const torch::Tensor& cos_sin,
+                                const torch::Tensor& positions,
+                                const torch::Tensor& slot_mapping) {
+  check_bf16_rowslice(q, "q", true);
+  check_bf16_rowslice(k, "k", true);
+  check_bf16_rowslice(v, "v", true);
+  TORCH_CHECK(k.stride(0) == v.stride(0), "k/v stride mismatch");
+  check_kv_caches(key_cache, value_cache, cache_dtype);
+  check_i32_gpu(positions, "positions");
+  check_i32_gpu(slot_mapping, "slot_mapping");
+  TORCH_CHECK(cos_sin.scalar_type() == torch::kFloat32 && cos_sin.is_cuda() &&
+              cos_sin.is_contiguous() && cos_sin.dim() == 2,
+              "cos_sin must be a contiguous 2-D fp32 GPU tensor");
+  const int64_t tokens = q.size(0);
+  const int64_t head_dim = key_cache.size(3);
+  const int64_t num_kv_heads = key_cache.size(1);
+  TORCH_CHECK(cos_sin.size(1) == head_dim,
+              "cos_sin row width must equal the cache head_dim");
+  TORCH_CHECK(k.size(0) == tokens && v.size(0) == tokens &&
+              positions.numel() == tokens && slot_mapping.numel() == tokens,
+              "q/k/v/positions/slot_mapping token counts differ");
+  const int64_t q_width = q.numel() / std::max<int64_t>(tokens, 1);
+  const int64_t k_width = k.numel() / std::max<int64_t>(tokens, 1);
+  const int64_t v_width = v.numel() / std::max<int64_t>(tokens, 1);
+  TORCH_CHECK(k_width == num_kv_heads * head_dim && v_width == k_width,
+              "k/v rows must be cache KVH * head_dim wide");
+  TORCH_CHECK(q_width % head_dim == 0,
+              "q row width must be a multiple of the cache head_dim");
+  // both kernels read V rows as 16-byte vectors
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(v.data_ptr()) % 16 == 0 &&
+              v.stride(0) % 8 == 0, "v rows must be 16-byte aligned");
+  RopeStoreLaunch a;
+  a.q = q.data_ptr();
+  a.k = k.data_ptr();
+  a.v = v.data_ptr();
+  a.key_cache = key_cache.data_ptr();
+  a.val_cache = value_cache.data_ptr();
+  a.cos_sin = cos_sin.data_ptr();
+  a.positions = positions.data_ptr();
+  a.slot_mapping = slot_mapping.data_ptr();
+  a.tokens = (int)tokens;
+  a.num_q_heads = (int)(q_width / head_dim);
+  a.num_kv_heads = (int)num_kv_heads;
+  a.head_dim = (int)head_dim;
+  a.page_size = (int)key_cache.size(2);
+  a.q_stride = (int)q.stride(0);
+  a.kv_stride = (int)k.stride(0);
+  a.k_inv_scale = 1.f;
+  a.v_inv_scale = 1.f;
+  return a;
 }
 
 void rope_store_kv(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                    torch::Tensor key_cache, torch::Tensor value_cache,
                    torch::Tensor cos_sin, torch::Tensor positions,
                    torch::Tensor slot_mapping) {
-  check_bf16_rowslice(q, "q");
-  check_bf16_rowslice(k, "k");
-  check_bf16_rowslice(v, "v");
-  TORCH_CHECK(k.stride(0) == v.stride(0), "k/v stride mismatch");
-  TORCH_CHECK(cos_sin.scalar_type() == torch::kFloat32, "cos_sin fp32");
-  TORCH_CHECK(positions.scalar_type() == torch::kInt32, "positions int32");
-  TORCH_CHECK(slot_mapping.scalar_type() == torch::kInt32, "slots int32");
-  check_kv_caches(key_cache, value_cache);
-  check_i32_gpu(positions, "positions");
-  check_i32_gpu(slot_mapping, "slot_mapping");
-  TORCH_CHECK(cos_sin.is_cuda() && cos_sin.is_contiguous() &&
-              cos_sin.dim() == 2, "cos_sin must be a contiguous 2-D GPU tensor");
-  const int tokens = q.size(0);
-  const int head_dim = key_cache.size(3);
-  const int num_kv_heads = key_cache.size(1);
-  const int page_size = key_cache.size(2);
-  TORCH_CHECK(cos_sin.size(1) == head_dim,
-              "cos_sin row width must equal the cache head_dim");
-  TORCH_CHECK(k.size(0) == tokens && v.size(0) == tokens &&
-              positions.numel() == tokens && slot_mapping.numel() == tokens,
-              "q/k/v/positions/slot_mapping token counts differ");
-  const int64_t q_width = q.numel() / std::max(tokens, 1);
-  const int64_t k_width = k.numel() / std::max(tokens, 1);
-  const int64_t v_width = v.numel() / std::max(tokens, 1);
-  TORCH_CHECK(k_width == (int64_t)num_kv_heads * head_dim && v_width == k_width,
-              "k/v rows must be cache KVH * head_dim wide");
-  TORCH_CHECK(q_width % head_dim == 0,
-              "q row width must be a multiple of the cache head_dim");
-  if (tokens == 0) return;
-  const int num_q_heads = (int)(q_width / head_dim);
-  launch_rope_store_kv(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                       key_cache.data_ptr(), value_cache.data_ptr(),
-                       cos_sin.data_ptr(), positions.data_ptr(),
-                       slot_mapping.data_ptr(), tokens, num_q_heads,
-                       num_kv_heads, head_dim, page_size,
-                       (int)q.stride(0), (int)k.stride(0),
-                       current_stream());
+  const RopeStoreLaunch a =
+      rope_store_args(q, k, v, key_cache, value_cache, torch::kBFloat16,
+                      cos_sin, positions, slot_mapping);
+  if (a.tokens == 0) return;
+  LAUNCH(launch_rope_store_kv, a, current_stream());
+}
+
+// ---- FP8 (OCP e4m3fn) paged KV cache --------------------------------------
+// Separate entry points: the bf16 ones keep rejecting every non-bf16 cache.
+
+void rope_store_kv_fp8(torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                       torch::Tensor key_cache, torch::Tensor value_cache,
+                       torch::Tensor cos_sin, torch::Tensor positions,
+                       torch::Tensor slot_mapping, int64_t k_scale_log2,
+                       int64_t v_scale_log2) {
+  RopeStoreLaunch a =
+      rope_store_args(q, k, v, key_cache, value_cache, torch::kFloat8_e4m3fn,
+                      cos_sin, positions, slot_mapping);
+  a.k_inv_scale = check_scale_log2(-k_scale_log2, "kv_k_scale_log2");
+  a.v_inv_scale = check_scale_log2(-v_scale_log2, "kv_v_scale_log2");
+  if (a.tokens == 0) return;
+  LAUNCH(launch_rope_store_kv_fp8, a, current_stream());
+}
+
+torch::Tensor kv_gather_dequant(torch::Tensor cache, torch::Tensor slots,
+                                int64_t scale_log2) {
+  check_kv_cache(cache, "cache", torch::kFloat8_e4m3fn);
+  check_i32_gpu(slots, "slots");
+  TORCH_CHECK(slots.dim() == 1 && slots.device() == cache.device(),
+              "slots must be 1-D on the cache's device");
+  const float scale = check_scale_log2(scale_log2, "scale_log2");
+  const int64_t tokens = slots.numel();
+  const int num_kv_heads = cache.size(1);
+  auto out = torch::empty({tokens, (int64_t)num_kv_heads, (int64_t)128},
+                          cache.options().dtype(torch::kBFloat16));
+  if (tokens == 0) return out;
+  LAUNCH(launch_kv_gather_dequant, out.data_ptr(), cache.data_ptr(),
+         slots.data_ptr(), (long)tokens,
+         (int)(cache.numel() / 128 / num_kv_heads), num_kv_heads,
+         (int)cache.size(2), scale, current_stream());
+  return out;
 }
 
 // How the partials of num_splits > 1 are merged.  combine 0: inside the
@@ -213,39 +269,42 @@ bool pick_in_wg_combine(int64_t combine, int64_t num_splits, bool mfma_pair,
                         const char* what) {
   TORCH_CHECK(combine >= 0 && combine <= 2,
               "combine must be 0 (auto), 1 (kernel) or 2 (in-workgroup)");
+  // the in-workgroup kernels run exactly WS = num_splits splits and get no
+  // partial buffers: never hand them another count
   const bool can = mfma_pair && (num_splits == 2 || num_splits == 4);
   TORCH_CHECK(combine != 2 || can, "combine = 2 needs ", what,
               ", a page size of 16 and 2 or 4 splits");
-  const bool in_wg = combine != 1 && can;
-  // the in-workgroup kernels run exactly WS = num_splits splits and get no
-  // partial buffers: never hand them another count
-  TORCH_CHECK(!in_wg || num_splits == 2 || num_splits == 4,
-              "in-workgroup combine with ", num_splits, " splits");
-  return in_wg;
+  return combine != 1 && can;
 }
 
-torch::Tensor decode_attention(torch::Tensor q, torch::Tensor key_cache,
-                               torch::Tensor value_cache,
-                               torch::Tensor block_tables,
-                               torch::Tensor context_lens, double scale,
-                               int64_t num_splits, int64_t variant,
-                               int64_t combine = 0) {
-  // q may be a slice of the fused QKV projection: 3-D bf16 with
-  // contiguous (head, dim) rows and an arbitrary token stride
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16 &&
-              q.dim() == 3 && q.stride(2) == 1 &&
-              q.stride(1) == q.size(2), "q must be [T, QH, D] row-sliced");
-  const int num_seqs = q.size(0);
-  const int num_q_heads = q.size(1);
-  const int head_dim = q.size(2);
-  TORCH_CHECK(head_dim == 128, "head_dim must be 128");
-  check_kv_caches(key_cache, value_cache);
+// What both decode bindings check, derive and allocate.  The launch struct
+// comes back complete but for the scale.
+struct DecodeGeometry {
+  DecodeLaunch launch;
+  int page_size;
+  torch::Tensor out, partial_o, partial_ml;
+};
+
+// pair_variant: the caller's kernel is a page-pair MFMA one wherever the
+// page size is 16 (variant 4, or the e4m3 kernel, named by `what`).
+DecodeGeometry decode_geometry(const torch::Tensor& q,
+                               const torch::Tensor& key_cache,
+                               const torch::Tensor& value_cache,
+                               torch::ScalarType cache_dtype,
+                               const torch::Tensor& block_tables,
+                               const torch::Tensor& context_lens,
+                               int64_t num_splits, int64_t combine,
+                               bool pair_variant, const char* what) {
+  // q may be a slice of the fused QKV projection
+  check_bf16_rowslice(q, "q");
+  const int64_t num_seqs = q.size(0), num_q_heads = q.size(1);
+  TORCH_CHECK(q.size(2) == 128, "head_dim must be 128");
+  check_kv_caches(key_cache, value_cache, cache_dtype);
   TORCH_CHECK(key_cache.size(3) == 128, "cache head_dim must be 128");
-  const int num_kv_heads = key_cache.size(1);
-  const int page_size = key_cache.size(2);
+  const int64_t num_kv_heads = key_cache.size(1);
   TORCH_CHECK(num_q_heads % num_kv_heads == 0,
               "q heads must be a multiple of the cache KV heads");
-  const int qpg = num_q_heads / num_kv_heads;
+  const int64_t qpg = num_q_heads / num_kv_heads;
   TORCH_CHECK(qpg == 1 || qpg == 2 || qpg == 4 || qpg == 8,
               "GQA group must be 1/2/4/8");
   check_i32_gpu(block_tables, "block_tables");
@@ -255,128 +314,51 @@ torch::Tensor decode_attention(torch::Tensor q, torch::Tensor key_cache,
   TORCH_CHECK(context_lens.dim() == 1 && context_lens.size(0) == num_seqs,
               "context_lens must be [num_seqs]");
   TORCH_CHECK(num_splits >= 1, "num_splits must be >= 1");
+  DecodeGeometry g;
+  g.page_size = (int)key_cache.size(2);
   const bool in_wg = pick_in_wg_combine(
-      combine, num_splits, variant == 4 && page_size == 16, "variant 4");
-  const int max_pages = block_tables.size(1);
-  auto out = torch::empty({num_seqs, num_q_heads, head_dim}, q.options());
-  if (num_seqs == 0) return out;
-  torch::Tensor partial_o, partial_ml;
-  void *po = nullptr, *pml = nullptr;
+      combine, num_splits, pair_variant && g.page_size == 16, what);
+  g.out = torch::empty({num_seqs, num_q_heads, 128}, q.options());
   if (num_splits > 1 && !in_wg) {
     auto opts = q.options().dtype(torch::kFloat32);
-    partial_o = torch::empty({num_splits, num_seqs, num_q_heads, head_dim}, opts);
-    partial_ml = torch::empty({num_splits, num_seqs, num_q_heads, 2}, opts);
-    po = partial_o.data_ptr();
-    pml = partial_ml.data_ptr();
+    g.partial_o = torch::empty({num_splits, num_seqs, num_q_heads, 128}, opts);
+    g.partial_ml = torch::empty({num_splits, num_seqs, num_q_heads, 2}, opts);
   }
-  launch_decode_attention(out.data_ptr(), po, pml, q.data_ptr(),
-                          key_cache.data_ptr(), value_cache.data_ptr(),
-                          block_tables.data_ptr(), context_lens.data_ptr(),
-                          (float)scale, num_seqs, num_q_heads, num_kv_heads,
-                          page_size, max_pages, (int)num_splits, (int)variant,
-                          (int)q.stride(0), in_wg, current_stream());
-  return out;
+  DecodeLaunch& a = g.launch;
+  a.out = g.out.data_ptr();
+  a.partial_o = g.partial_o.defined() ? g.partial_o.data_ptr() : nullptr;
+  a.partial_ml = g.partial_ml.defined() ? g.partial_ml.data_ptr() : nullptr;
+  a.q = q.data_ptr();
+  a.key_cache = key_cache.data_ptr();
+  a.val_cache = value_cache.data_ptr();
+  a.block_tables = block_tables.data_ptr();
+  a.context_lens = context_lens.data_ptr();
+  a.scale = 0.f;
+  a.num_seqs = (int)num_seqs;
+  a.num_q_heads = (int)num_q_heads;
+  a.num_kv_heads = (int)num_kv_heads;
+  a.max_pages = (int)block_tables.size(1);
+  a.num_splits = (int)num_splits;
+  a.q_stride = (int)q.stride(0);
+  a.in_wg = in_wg;
+  return g;
 }
 
-// ---- FP8 (OCP e4m3fn) paged KV cache --------------------------------------
-// Separate entry points: the bf16 ones above keep rejecting every non-bf16
-// cache.  Scales are powers of two given as integer exponents.
-
-float check_scale_log2(int64_t e, const char* name) {
-  TORCH_CHECK(e >= -16 && e <= 16, name, " must be in [-16, 16], got ", e);
-  return std::ldexp(1.0f, (int)e);
-}
-
-void check_fp8_cache(const torch::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
-  TORCH_CHECK(t.scalar_type() == torch::kFloat8_e4m3fn, name,
-              " must be float8_e4m3fn");
-  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-  TORCH_CHECK(t.dim() == 4, name,
-              " must be [pages, KVH, page_size, head_dim]");
-  const int64_t page_size = t.size(2);
-  TORCH_CHECK(page_size > 0 && (page_size & (page_size - 1)) == 0,
-              "page_size must be a power of two");
-  TORCH_CHECK(t.size(1) > 0, "cache needs at least one KV head");
-  TORCH_CHECK(t.size(3) == 128, "fp8 cache head_dim must be 128");
-  TORCH_CHECK(t.numel() / 128 <= INT32_MAX, "cache has too many slots");
-}
-
-void check_fp8_caches(const torch::Tensor& key_cache,
-                      const torch::Tensor& value_cache) {
-  TORCH_CHECK(key_cache.scalar_type() == value_cache.scalar_type(),
-              "key_cache/value_cache dtype mismatch");
-  check_fp8_cache(key_cache, "key_cache");
-  check_fp8_cache(value_cache, "value_cache");
-  TORCH_CHECK(value_cache.sizes() == key_cache.sizes(),
-              "key_cache/value_cache shape mismatch");
-  TORCH_CHECK(value_cache.device() == key_cache.device(),
-              "key_cache/value_cache device mismatch");
-}
-
-void rope_store_kv_fp8(torch::Tensor q, torch::Tensor k, torch::Tensor v,
-                       torch::Tensor key_cache, torch::Tensor value_cache,
-                       torch::Tensor cos_sin, torch::Tensor positions,
-                       torch::Tensor slot_mapping, int64_t k_scale_log2,
-                       int64_t v_scale_log2) {
-  check_bf16_rowslice(q, "q");
-  check_bf16_rowslice(k, "k");
-  check_bf16_rowslice(v, "v");
-  TORCH_CHECK(k.stride(0) == v.stride(0), "k/v stride mismatch");
-  check_fp8_caches(key_cache, value_cache);
-  const float k_inv = check_scale_log2(-k_scale_log2, "kv_k_scale_log2");
-  const float v_inv = check_scale_log2(-v_scale_log2, "kv_v_scale_log2");
-  check_i32_gpu(positions, "positions");
-  check_i32_gpu(slot_mapping, "slot_mapping");
-  TORCH_CHECK(cos_sin.scalar_type() == torch::kFloat32 && cos_sin.is_cuda() &&
-              cos_sin.is_contiguous() && cos_sin.dim() == 2,
-              "cos_sin must be a contiguous 2-D fp32 GPU tensor");
-  const int tokens = q.size(0);
-  const int num_kv_heads = key_cache.size(1);
-  const int page_size = key_cache.size(2);
-  TORCH_CHECK(cos_sin.size(1) == 128,
-              "cos_sin row width must equal the cache head_dim");
-  TORCH_CHECK(k.size(0) == tokens && v.size(0) == tokens &&
-              positions.numel() == tokens && slot_mapping.numel() == tokens,
-              "q/k/v/positions/slot_mapping token counts differ");
-  const int64_t q_width = q.numel() / std::max(tokens, 1);
-  const int64_t k_width = k.numel() / std::max(tokens, 1);
-  const int64_t v_width = v.numel() / std::max(tokens, 1);
-  TORCH_CHECK(k_width == (int64_t)num_kv_heads * 128 && v_width == k_width,
-              "k/v rows must be cache KVH * head_dim wide");
-  TORCH_CHECK(q_width % 128 == 0,
-              "q row width must be a multiple of the cache head_dim");
-  // V rows are read as 16-byte vectors
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(v.data_ptr()) % 16 == 0 &&
-              v.stride(0) % 8 == 0, "v rows must be 16-byte aligned");
-  if (tokens == 0) return;
-  launch_rope_store_kv_fp8(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                           key_cache.data_ptr(), value_cache.data_ptr(),
-                           cos_sin.data_ptr(), positions.data_ptr(),
-                           slot_mapping.data_ptr(), tokens,
-                           (int)(q_width / 128), num_kv_heads, page_size,
-                           (int)q.stride(0), (int)k.stride(0), k_inv, v_inv,
-                           current_stream());
-}
-
-torch::Tensor kv_gather_dequant(torch::Tensor cache, torch::Tensor slots,
-                                int64_t scale_log2) {
-  check_fp8_cache(cache, "cache");
-  check_i32_gpu(slots, "slots");
-  TORCH_CHECK(slots.dim() == 1 && slots.device() == cache.device(),
-              "slots must be 1-D on the cache's device");
-  const float scale = check_scale_log2(scale_log2, "scale_log2");
-  const int64_t tokens = slots.numel();
-  const int num_kv_heads = cache.size(1);
-  auto out = torch::empty({tokens, (int64_t)num_kv_heads, (int64_t)128},
-                          cache.options().dtype(torch::kBFloat16));
-  if (tokens == 0) return out;
-  launch_kv_gather_dequant(out.data_ptr(), cache.data_ptr(), slots.data_ptr(),
-                           (long)tokens, (int)(cache.numel() / 128 /
-                                               num_kv_heads),
-                           num_kv_heads, (int)cache.size(2), scale,
-                           current_stream());
-  return out;
+torch::Tensor decode_attention(torch::Tensor q, torch::Tensor key_cache,
+                               torch::Tensor value_cache,
+                               torch::Tensor block_tables,
+                               torch::Tensor context_lens, double scale,
+                               int64_t num_splits, int64_t variant,
+                               int64_t combine = 0) {
+  DecodeGeometry g = decode_geometry(q, key_cache, value_cache,
+                                     torch::kBFloat16, block_tables,
+                                     context_lens, num_splits, combine,
+                                     variant == 4, "variant 4");
+  if (g.launch.num_seqs == 0) return g.out;
+  g.launch.scale = (float)scale;
+  LAUNCH(launch_decode_attention, g.launch, g.page_size, (int)variant,
+         current_stream());
+  return g.out;
 }
 
 torch::Tensor decode_attention_fp8(torch::Tensor q, torch::Tensor key_cache,
@@ -386,99 +368,81 @@ torch::Tensor decode_attention_fp8(torch::Tensor q, torch::Tensor key_cache,
                                    int64_t num_splits, int64_t k_scale_log2,
                                    int64_t v_scale_log2,
                                    int64_t combine = 0) {
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16 &&
-              q.dim() == 3 && q.stride(2) == 1 &&
-              q.stride(1) == q.size(2), "q must be [T, QH, D] row-sliced");
-  const int num_seqs = q.size(0);
-  const int num_q_heads = q.size(1);
-  TORCH_CHECK(q.size(2) == 128, "head_dim must be 128");
-  check_fp8_caches(key_cache, value_cache);
-  TORCH_CHECK(key_cache.size(2) == 16,
-              "fp8 decode needs a page size of 16");
+  DecodeGeometry g = decode_geometry(q, key_cache, value_cache,
+                                     torch::kFloat8_e4m3fn, block_tables,
+                                     context_lens, num_splits, combine, true,
+                                     "the fp8 kernel");
+  TORCH_CHECK(g.page_size == 16, "fp8 decode needs a page size of 16");
   const float k_scale = check_scale_log2(k_scale_log2, "kv_k_scale_log2");
   const float v_scale = check_scale_log2(v_scale_log2, "kv_v_scale_log2");
-  const int num_kv_heads = key_cache.size(1);
-  TORCH_CHECK(num_q_heads % num_kv_heads == 0,
-              "q heads must be a multiple of the cache KV heads");
-  const int qpg = num_q_heads / num_kv_heads;
-  TORCH_CHECK(qpg == 1 || qpg == 2 || qpg == 4 || qpg == 8,
-              "GQA group must be 1/2/4/8");
-  check_i32_gpu(block_tables, "block_tables");
-  check_i32_gpu(context_lens, "context_lens");
-  TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(0) == num_seqs,
-              "block_tables must be [num_seqs, max_pages]");
-  TORCH_CHECK(context_lens.dim() == 1 && context_lens.size(0) == num_seqs,
-              "context_lens must be [num_seqs]");
-  TORCH_CHECK(num_splits >= 1, "num_splits must be >= 1");
-  const bool in_wg =
-      pick_in_wg_combine(combine, num_splits, true, "the fp8 kernel");
-  const int max_pages = block_tables.size(1);
-  auto out = torch::empty({num_seqs, num_q_heads, 128}, q.options());
-  if (num_seqs == 0) return out;
-  torch::Tensor partial_o, partial_ml;
-  void *po = nullptr, *pml = nullptr;
-  if (num_splits > 1 && !in_wg) {
-    auto opts = q.options().dtype(torch::kFloat32);
-    partial_o = torch::empty({num_splits, num_seqs, num_q_heads, 128}, opts);
-    partial_ml = torch::empty({num_splits, num_seqs, num_q_heads, 2}, opts);
-    po = partial_o.data_ptr();
-    pml = partial_ml.data_ptr();
-  }
+  if (g.launch.num_seqs == 0) return g.out;
   // 2^ek folds into the score scale: a power of two, so the product is exact
-  launch_decode_attention_fp8(out.data_ptr(), po, pml, q.data_ptr(),
-                              key_cache.data_ptr(), value_cache.data_ptr(),
-                              block_tables.data_ptr(),
-                              context_lens.data_ptr(), (float)scale * k_scale,
-                              v_scale, num_seqs, num_q_heads, num_kv_heads,
-                              max_pages, (int)num_splits, (int)q.stride(0),
-                              in_wg, current_stream());
-  return out;
+  g.launch.scale = (float)scale * k_scale;
+  LAUNCH(launch_decode_attention_fp8, g.launch, v_scale, current_stream());
+  return g.out;
 }
 
 torch::Tensor prefill_attention(torch::Tensor q, torch::Tensor k,
                                 torch::Tensor v, torch::Tensor block_info,
                                 torch::Tensor seq_lens, double scale,
                                 int64_t swz) {
-  auto rowsliced3 = [](const torch::Tensor& t, const char* name) {
-    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kBFloat16 &&
-                t.dim() == 3 && t.stride(2) == 1 &&
-                t.stride(1) == t.size(2), name,
-                " must be [T, H, D] row-sliced");
-  };
-  rowsliced3(q, "q");
-  rowsliced3(k, "k");
-  rowsliced3(v, "v");
+  check_bf16_rowslice(q, "q");
+  check_bf16_rowslice(k, "k");
+  check_bf16_rowslice(v, "v");
+  TORCH_CHECK(k.device() == q.device() && v.device() == q.device(),
+              "q/k/v device mismatch");
+  TORCH_CHECK(k.sizes() == v.sizes(), "k/v shape mismatch");
   TORCH_CHECK(k.stride(0) == v.stride(0), "k/v stride mismatch");
-  TORCH_CHECK(q.size(2) == 128, "head_dim must be 128");
-  TORCH_CHECK(block_info.scalar_type() == torch::kInt32, "block_info int32");
-  TORCH_CHECK(seq_lens.scalar_type() == torch::kInt32, "seq_lens int32");
-  const int nblocks = block_info.size(0);
-  const int num_q_heads = q.size(1);
-  const int num_kv_heads = k.size(1);
-  auto out = torch::empty({q.size(0), (int64_t)num_q_heads, (int64_t)128},
-                          q.options());
-  launch_prefill_attention(out.data_ptr(), q.data_ptr(), k.data_ptr(),
-                           v.data_ptr(), block_info.data_ptr(),
-                           seq_lens.data_ptr(), (float)scale, nblocks,
-                           num_q_heads, num_kv_heads, (int)swz,
-                           (int)q.stride(0), (int)k.stride(0),
-                           current_stream());
+  TORCH_CHECK(q.size(2) == 128 && k.size(2) == 128, "head_dim must be 128");
+  const int64_t num_q_heads = q.size(1), num_kv_heads = k.size(1);
+  TORCH_CHECK(num_kv_heads >= 1 && num_q_heads % num_kv_heads == 0,
+              "q heads must be a multiple of the (>= 1) KV heads");
+  // reference.prefill_block_info: one row of 4 and one KV length per block
+  check_i32_gpu(block_info, "block_info");
+  check_i32_gpu(seq_lens, "seq_lens");
+  TORCH_CHECK(block_info.device() == q.device() &&
+              seq_lens.device() == q.device(),
+              "block_info and seq_lens must be on q's device");
+  TORCH_CHECK(block_info.dim() == 2 && block_info.size(1) == 4,
+              "block_info must be [nblocks, 4]");
+  const int64_t nblocks = block_info.size(0);
+  TORCH_CHECK(seq_lens.dim() == 1 && seq_lens.size(0) == nblocks,
+              "seq_lens must be [nblocks]");
+  // the grid is one workgroup per (block, q head)
+  TORCH_CHECK(nblocks * num_q_heads <= INT32_MAX, "too many blocks");
+  auto out = torch::empty({q.size(0), num_q_heads, 128}, q.options());
+  if (q.size(0) == 0 || nblocks == 0) return out;
+  PrefillLaunch a;
+  a.out = out.data_ptr();
+  a.q = q.data_ptr();
+  a.k = k.data_ptr();
+  a.v = v.data_ptr();
+  a.block_info = block_info.data_ptr();
+  a.seq_lens = seq_lens.data_ptr();
+  a.scale = (float)scale;
+  a.nblocks = (int)nblocks;
+  a.num_q_heads = (int)num_q_heads;
+  a.num_kv_heads = (int)num_kv_heads;
+  a.swz = (int)swz;
+  a.q_stride = (int)q.stride(0);
+  a.kv_stride = (int)k.stride(0);
+  LAUNCH(launch_prefill_attention, a, current_stream());
   return out;
 }
 
 torch::Tensor mfma_probe(torch::Tensor a, torch::Tensor b, int64_t a_split,
                          int64_t b_split) {
   auto d = torch::zeros({16, 16}, a.options().dtype(torch::kFloat32));
-  launch_mfma_probe(d.data_ptr(), a.data_ptr(), b.data_ptr(), (int)a_split,
-                    (int)b_split, current_stream());
+  LAUNCH(launch_mfma_probe, d.data_ptr(), a.data_ptr(), b.data_ptr(),
+         (int)a_split, (int)b_split, current_stream());
   return d;
 }
 
 torch::Tensor mfma_probe32(torch::Tensor a, torch::Tensor b, int64_t a_split,
                            int64_t b_split, int64_t dmap) {
   auto d = torch::zeros({32, 32}, a.options().dtype(torch::kFloat32));
-  launch_mfma_probe32(d.data_ptr(), a.data_ptr(), b.data_ptr(), (int)a_split,
-                      (int)b_split, (int)dmap, current_stream());
+  LAUNCH(launch_mfma_probe32, d.data_ptr(), a.data_ptr(), b.data_ptr(),
+         (int)a_split, (int)b_split, (int)dmap, current_stream());
   return d;
 }
 
@@ -558,9 +522,12 @@ int skinny_gemm_launch(const torch::Tensor& a, const torch::Tensor& w,
     c = torch::empty({M, N}, a.options());
     cp = c.data_ptr();
   }
-  (panel == 64 ? launch_skinny_gemm_wide : launch_skinny_gemm)(
-      cp, wsp, a.data_ptr(), w.data_ptr(), (int)M, (int)N, (int)K, splits,
-      current_stream());
+  if (panel == 64)
+    LAUNCH(launch_skinny_gemm_wide, cp, wsp, a.data_ptr(), w.data_ptr(),
+           (int)M, (int)N, (int)K, splits, current_stream());
+  else
+    LAUNCH(launch_skinny_gemm, cp, wsp, a.data_ptr(), w.data_ptr(), (int)M,
+           (int)N, (int)K, splits, current_stream());
   return splits;
 }
 
@@ -572,8 +539,8 @@ torch::Tensor skinny_gemm(torch::Tensor a, torch::Tensor w,
   const int splits = skinny_gemm_launch(a, w, force_splits, panel, c, ws);
   if (splits > 1) {
     c = torch::empty({a.size(0), w.size(0)}, a.options());
-    launch_reduce_splits(c.data_ptr(), ws.data_ptr(), splits,
-                         (long)c.numel(), current_stream());
+    LAUNCH(launch_reduce_splits, c.data_ptr(), ws.data_ptr(), splits,
+           (long)c.numel(), current_stream());
   }
   return c;
 }
@@ -602,15 +569,14 @@ torch::Tensor skinny_gemm_add_rmsnorm(torch::Tensor a, torch::Tensor w,
   const int splits = skinny_gemm_launch(a, w, force_splits, panel, c, ws);
   const int M = (int)a.size(0), N = (int)w.size(0);
   if (splits == 1) {
-    launch_fused_add_rmsnorm(c.data_ptr(), residual.data_ptr(),
-                             norm_weight.data_ptr(), (float)eps, M, N,
-                             current_stream());
+    LAUNCH(launch_fused_add_rmsnorm, c.data_ptr(), residual.data_ptr(),
+           norm_weight.data_ptr(), (float)eps, M, N, current_stream());
     return c;
   }
   c = torch::empty({a.size(0), w.size(0)}, a.options());
-  launch_fold_add_rmsnorm(c.data_ptr(), ws.data_ptr(), residual.data_ptr(),
-                          norm_weight.data_ptr(), (float)eps, splits, M, N,
-                          current_stream());
+  LAUNCH(launch_fold_add_rmsnorm, c.data_ptr(), ws.data_ptr(),
+         residual.data_ptr(), norm_weight.data_ptr(), (float)eps, splits, M,
+         N, current_stream());
   return c;
 }
 
@@ -648,10 +614,10 @@ std::vector<torch::Tensor> sample(torch::Tensor logits,
   auto tokens = torch::empty({n}, logits.options().dtype(torch::kInt64));
   auto kept = torch::empty({n}, logits.options().dtype(torch::kInt32));
   if (n == 0) return {tokens, kept};
-  launch_sample(tokens.data_ptr(), kept.data_ptr(), logits.data_ptr(),
-                temperature.data_ptr(), top_k.data_ptr(), top_p.data_ptr(),
-                min_p.data_ptr(), seed.data_ptr(), pos.data_ptr(), (int)n,
-                (int)V, current_stream());
+  LAUNCH(launch_sample, tokens.data_ptr(), kept.data_ptr(),
+         logits.data_ptr(), temperature.data_ptr(), top_k.data_ptr(),
+         top_p.data_ptr(), min_p.data_ptr(), seed.data_ptr(), pos.data_ptr(),
+         (int)n, (int)V, current_stream());
   return {tokens, kept};
 }
 
@@ -661,23 +627,7 @@ std::vector<torch::Tensor> sample(torch::Tensor logits,
 // requires; the prefill process maps it with lazy peer access (the xGMI
 // route) and pushes pages with the kv_peer_copy kernel.
 
-torch::Tensor ipc_alloc_bf16(std::vector<int64_t> sizes) {
-  int64_t numel = 1;
-  for (auto s : sizes) numel *= s;
-  void* ptr = nullptr;
-  hipError_t err = hipMalloc(&ptr, numel * 2);
-  TORCH_CHECK(err == hipSuccess, "hipMalloc(", numel * 2,
-              " B) failed: ", hipGetErrorString(err));
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  auto opts = torch::TensorOptions()
-                  .dtype(torch::kBFloat16)
-                  .device(torch::kCUDA, dev);
-  return torch::from_blob(
-      ptr, sizes, [](void* p) { (void)hipFree(p); }, opts);
-}
-
-// The same allocation for any element type (the fp8 KV pool).
+// hipMalloc-backed tensor of any element type (bf16 and e4m3 KV pools).
 torch::Tensor ipc_alloc(std::vector<int64_t> sizes, torch::ScalarType dtype) {
   int64_t numel = 1;
   for (auto s : sizes) numel *= s;
@@ -691,6 +641,10 @@ torch::Tensor ipc_alloc(std::vector<int64_t> sizes, torch::ScalarType dtype) {
   auto opts = torch::TensorOptions().dtype(dtype).device(torch::kCUDA, dev);
   return torch::from_blob(
       ptr, sizes, [](void* p) { (void)hipFree(p); }, opts);
+}
+
+torch::Tensor ipc_alloc_bf16(std::vector<int64_t> sizes) {
+  return ipc_alloc(std::move(sizes), torch::kBFloat16);
 }
 
 py::bytes kv_ipc_export(torch::Tensor pool) {
@@ -754,11 +708,19 @@ void kv_peer_copy(int64_t dst_base, torch::Tensor src_kv,
                            (long)src_kv.element_size();
   TORCH_CHECK(chunk_bytes % 16 == 0, "chunk must be 16B-aligned");
   const long chunk_vec = chunk_bytes / 16;  // uint4 vectors
-  launch_kv_peer_copy(reinterpret_cast<void*>(dst_base), src_kv.data_ptr(),
-                      src_pages.data_ptr(), dst_pages.data_ptr(), n_pages,
-                      2 * layers, (int)chunk_vec, chunk_vec,
-                      chunk_vec, Ps * chunk_vec, dst_num_pages * chunk_vec,
-                      current_stream());
+  KvPeerCopyLaunch a;
+  a.dst_base = reinterpret_cast<void*>(dst_base);
+  a.src_base = src_kv.data_ptr();
+  a.src_pages = src_pages.data_ptr();
+  a.dst_pages = dst_pages.data_ptr();
+  a.n_pages = n_pages;
+  a.n_chunks = 2 * layers;
+  a.chunk_vec = (int)chunk_vec;
+  a.src_page_stride_vec = chunk_vec;
+  a.dst_page_stride_vec = chunk_vec;
+  a.src_chunk_stride_vec = Ps * chunk_vec;
+  a.dst_chunk_stride_vec = dst_num_pages * chunk_vec;
+  LAUNCH(launch_kv_peer_copy, a, current_stream());
 }
 
 // ---- one-shot xGMI all-reduce (parallel/xgmi_allreduce.py) ---------------
@@ -822,8 +784,8 @@ torch::Tensor xgmi_allreduce(torch::Tensor inp,
     sp[i] = reinterpret_cast<void*>(sig_ptrs[i]);
     dp[i] = reinterpret_cast<void*>(data_ptrs[i]);
   }
-  launch_xgmi_allreduce(out.data_ptr(), inp.data_ptr(), sp, dp, world,
-                        (int)rank, (long)inp.numel(), current_stream());
+  LAUNCH(launch_xgmi_allreduce, out.data_ptr(), inp.data_ptr(), sp, dp, world,
+         (int)rank, (long)inp.numel(), current_stream());
   return out;
 }
 

@@ -92,11 +92,3 @@ DEV_INLINE float block_sum(float x, float* scratch /* NW floats */) {
 }
 
 DEV_INLINE int cdiv(int a, int b) { return (a + b - 1) / b; }
-
-#define HIP_KERNEL_CHECK()                                                    \
-  do {                                                                        \
-    hipError_t err_ = hipGetLastError();                                      \
-    if (err_ != hipSuccess) {                                                 \
-      printf("HIP kernel launch error: %s\n", hipGetErrorString(err_));       \
-    }                                                                         \
-  } while (0)

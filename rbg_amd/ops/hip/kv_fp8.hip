@@ -7,6 +7,7 @@
 // (docs/FEATURES.md "FP8 KV cache").  Both scalings are by powers of two and
 // therefore exact, so every reader agrees on what a cached value is.
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -176,26 +177,24 @@ __global__ void kv_gather_dequant_kernel(
 
 extern "C" {
 
-void launch_rope_store_kv_fp8(void* q, void* k, const void* v, void* key_cache,
-                              void* val_cache, const void* cos_sin,
-                              const void* positions, const void* slot_mapping,
-                              int tokens, int num_q_heads, int num_kv_heads,
-                              int page_size, int q_stride, int kv_stride,
-                              float k_inv_scale, float v_inv_scale,
-                              hipStream_t stream) {
-  hipLaunchKernelGGL(rope_store_kv_fp8_kernel, dim3(tokens), dim3(256), 0,
-                     stream, (__hip_bfloat16*)q, (__hip_bfloat16*)k,
-                     (const __hip_bfloat16*)v, (uint8_t*)key_cache,
-                     (uint8_t*)val_cache, (const float*)cos_sin,
-                     (const int*)positions, (const int*)slot_mapping,
-                     num_q_heads, num_kv_heads, page_size, q_stride,
-                     kv_stride, k_inv_scale, v_inv_scale);
+hipError_t launch_rope_store_kv_fp8(const RopeStoreLaunch& a,
+                                    hipStream_t stream) {
+  if (a.head_dim != 128) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rope_store_kv_fp8_kernel, dim3(a.tokens), dim3(256), 0,
+                     stream, (__hip_bfloat16*)a.q, (__hip_bfloat16*)a.k,
+                     (const __hip_bfloat16*)a.v, (uint8_t*)a.key_cache,
+                     (uint8_t*)a.val_cache, (const float*)a.cos_sin,
+                     (const int*)a.positions, (const int*)a.slot_mapping,
+                     a.num_q_heads, a.num_kv_heads, a.page_size, a.q_stride,
+                     a.kv_stride, a.k_inv_scale, a.v_inv_scale);
+  return hipGetLastError();
 }
 
-void launch_kv_gather_dequant(void* out, const void* cache, const void* slots,
-                              long tokens, int num_slots, int num_kv_heads,
-                              int page_size, float scale,
-                              hipStream_t stream) {
+hipError_t launch_kv_gather_dequant(void* out, const void* cache,
+                                    const void* slots, long tokens,
+                                    int num_slots, int num_kv_heads,
+                                    int page_size, float scale,
+                                    hipStream_t stream) {
   const long total = tokens * num_kv_heads * 8;
   const int block = 256;
   const long grid = (total + block - 1) / block;
@@ -203,6 +202,7 @@ void launch_kv_gather_dequant(void* out, const void* cache, const void* slots,
                      dim3(block), 0, stream, (__hip_bfloat16*)out,
                      (const uint8_t*)cache, (const int*)slots, total,
                      num_slots, num_kv_heads, page_size, scale);
+  return hipGetLastError();
 }
 
 }  // extern "C"

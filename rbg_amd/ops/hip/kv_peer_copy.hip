@@ -25,6 +25,7 @@
 // the pool layout makes a page 2*L discontiguous 32 KB chunks — thousands of
 // SDMA submissions per sequence would be launch-bound, one kernel is not).
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -57,19 +58,15 @@ __global__ void kv_peer_copy_kernel(
 
 }  // namespace
 
-extern "C" void launch_kv_peer_copy(
-    void* dst_base, const void* src_base, const void* src_pages,
-    const void* dst_pages, int n_pages, int n_chunks, int chunk_vec,
-    long src_page_stride_vec, long dst_page_stride_vec,
-    long src_chunk_stride_vec, long dst_chunk_stride_vec,
-    hipStream_t stream) {
-  dim3 grid(n_pages, n_chunks);
-  const int threads = chunk_vec >= 256 ? 256 : 64;
+extern "C" hipError_t launch_kv_peer_copy(const KvPeerCopyLaunch& a,
+                                          hipStream_t stream) {
+  dim3 grid(a.n_pages, a.n_chunks);
+  const int threads = a.chunk_vec >= 256 ? 256 : 64;
   hipLaunchKernelGGL(kv_peer_copy_kernel, grid, dim3(threads), 0, stream,
-                     (uint4*)dst_base, (const uint4*)src_base,
-                     (const int*)src_pages, (const int*)dst_pages, n_pages,
-                     n_chunks, chunk_vec, src_page_stride_vec,
-                     dst_page_stride_vec, src_chunk_stride_vec,
-                     dst_chunk_stride_vec);
-  HIP_KERNEL_CHECK();
+                     (uint4*)a.dst_base, (const uint4*)a.src_base,
+                     (const int*)a.src_pages, (const int*)a.dst_pages,
+                     a.n_pages, a.n_chunks, a.chunk_vec,
+                     a.src_page_stride_vec, a.dst_page_stride_vec,
+                     a.src_chunk_stride_vec, a.dst_chunk_stride_vec);
+  return hipGetLastError();
 }

@@ -6,6 +6,7 @@
 // lane->element mapping with asymmetric operands).  The C/D mapping is taken
 // as col=lane&15, row=4*(lane>>4)+reg and itself verified by the refcheck.
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -77,15 +78,16 @@ __global__ void mfma_probe32_kernel(
 
 extern "C" {
 
-void launch_mfma_probe32(void* d, const void* a, const void* b, int a_split,
-                         int b_split, int dmap, hipStream_t stream) {
+hipError_t launch_mfma_probe32(void* d, const void* a, const void* b,
+                               int a_split, int b_split, int dmap,
+                               hipStream_t stream) {
   dim3 grid(1), block(64);
 #define CASE32(AS, BS, DM)                                                   \
   hipLaunchKernelGGL((mfma_probe32_kernel<AS, BS, DM>), grid, block, 0,      \
                      stream, (float*)d, (const __hip_bfloat16*)a,            \
                      (const __hip_bfloat16*)b)
-  const int key = a_split * 4 + b_split * 2 + dmap;
-  switch (key) {
+  if ((a_split | b_split | dmap) & ~1) return hipErrorInvalidValue;
+  switch (a_split * 4 + b_split * 2 + dmap) {
     case 0: CASE32(0, 0, 0); break;
     case 1: CASE32(0, 0, 1); break;
     case 2: CASE32(0, 1, 0); break;
@@ -96,10 +98,11 @@ void launch_mfma_probe32(void* d, const void* a, const void* b, int a_split,
     case 7: CASE32(1, 1, 1); break;
   }
 #undef CASE32
+  return hipGetLastError();
 }
 
-void launch_mfma_probe(void* d, const void* a, const void* b, int a_split,
-                       int b_split, hipStream_t stream) {
+hipError_t launch_mfma_probe(void* d, const void* a, const void* b,
+                             int a_split, int b_split, hipStream_t stream) {
   dim3 grid(1), block(64);
 #define CASE(AS, BS)                                                       \
   hipLaunchKernelGGL((mfma_probe_kernel<AS, BS>), grid, block, 0, stream,  \
@@ -108,8 +111,10 @@ void launch_mfma_probe(void* d, const void* a, const void* b, int a_split,
   if (a_split == 0 && b_split == 0) CASE(0, 0);
   else if (a_split == 0 && b_split == 1) CASE(0, 1);
   else if (a_split == 1 && b_split == 0) CASE(1, 0);
-  else CASE(1, 1);
+  else if (a_split == 1 && b_split == 1) CASE(1, 1);
+  else return hipErrorInvalidValue;
 #undef CASE
+  return hipGetLastError();
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 // Capability analog: the RMSNorm the reference delegates to SGLang engines
 // (SURVEY §2.3 prefill/decode engine rows).
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -111,31 +112,35 @@ __global__ void rmsnorm_kernel(__hip_bfloat16* __restrict__ out,      // [T,H]
 
 extern "C" {
 
-void launch_rmsnorm(void* out, void* input, const void* weight, float eps,
-                    int tokens, int hidden, hipStream_t stream) {
+hipError_t launch_rmsnorm(void* out, void* input, const void* weight,
+                          float eps, int tokens, int hidden,
+                          hipStream_t stream) {
   dim3 grid(tokens), block(256);
   hipLaunchKernelGGL(rmsnorm_kernel<NORM_PLAIN>, grid, block, 0, stream,
                      (__hip_bfloat16*)out, (__hip_bfloat16*)input,
                      (__hip_bfloat16*)nullptr, (const __hip_bfloat16*)weight,
                      (const float*)nullptr, eps, hidden);
+  return hipGetLastError();
 }
 
 // input := rmsnorm(input + residual); residual := input + residual
-void launch_fused_add_rmsnorm(void* input, void* residual, const void* weight,
-                              float eps, int tokens, int hidden,
-                              hipStream_t stream) {
+hipError_t launch_fused_add_rmsnorm(void* input, void* residual,
+                                    const void* weight, float eps, int tokens,
+                                    int hidden, hipStream_t stream) {
   dim3 grid(tokens), block(256);
   hipLaunchKernelGGL(rmsnorm_kernel<NORM_FUSED_ADD>, grid, block, 0, stream,
                      (__hip_bfloat16*)input, (__hip_bfloat16*)input,
                      (__hip_bfloat16*)residual, (const __hip_bfloat16*)weight,
                      (const float*)nullptr, eps, hidden);
+  return hipGetLastError();
 }
 
 // x := bf16(sum_s ws[s]); out := rmsnorm(x + residual); residual := x + residual
-// splits is 2, 4 or 8 (checked in bindings.cpp)
-void launch_fold_add_rmsnorm(void* out, const void* ws, void* residual,
-                             const void* weight, float eps, int splits,
-                             int tokens, int hidden, hipStream_t stream) {
+// for splits 2, 4 or 8
+hipError_t launch_fold_add_rmsnorm(void* out, const void* ws, void* residual,
+                                   const void* weight, float eps, int splits,
+                                   int tokens, int hidden,
+                                   hipStream_t stream) {
   dim3 grid(tokens), block(256);
 #define LAUNCH_FOLD(S)                                                       \
   hipLaunchKernelGGL((rmsnorm_kernel<NORM_FOLD_ADD, S>), grid, block, 0,      \
@@ -145,8 +150,10 @@ void launch_fold_add_rmsnorm(void* out, const void* ws, void* residual,
                      hidden)
   if (splits == 2) LAUNCH_FOLD(2);
   else if (splits == 4) LAUNCH_FOLD(4);
-  else LAUNCH_FOLD(8);
+  else if (splits == 8) LAUNCH_FOLD(8);
+  else return hipErrorInvalidValue;
 #undef LAUNCH_FOLD
+  return hipGetLastError();
 }
 
 }  // extern "C"

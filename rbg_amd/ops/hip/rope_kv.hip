@@ -10,6 +10,7 @@
 // Capability analog: RoPE + KV-cache insert of the engines the reference
 // orchestrates.
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -89,20 +90,16 @@ __global__ void rope_store_kv_kernel(
 
 extern "C" {
 
-void launch_rope_store_kv(void* q, void* k, const void* v, void* key_cache,
-                          void* val_cache, const void* cos_sin,
-                          const void* positions, const void* slot_mapping,
-                          int tokens, int num_q_heads, int num_kv_heads,
-                          int head_dim, int page_size, int q_stride,
-                          int kv_stride, hipStream_t stream) {
-  dim3 grid(tokens), block(256);
+hipError_t launch_rope_store_kv(const RopeStoreLaunch& a, hipStream_t stream) {
+  dim3 grid(a.tokens), block(256);
   hipLaunchKernelGGL(rope_store_kv_kernel, grid, block, 0, stream,
-                     (__hip_bfloat16*)q, (__hip_bfloat16*)k,
-                     (const __hip_bfloat16*)v, (__hip_bfloat16*)key_cache,
-                     (__hip_bfloat16*)val_cache, (const float*)cos_sin,
-                     (const int*)positions, (const int*)slot_mapping,
-                     num_q_heads, num_kv_heads, head_dim, page_size,
-                     q_stride, kv_stride);
+                     (__hip_bfloat16*)a.q, (__hip_bfloat16*)a.k,
+                     (const __hip_bfloat16*)a.v, (__hip_bfloat16*)a.key_cache,
+                     (__hip_bfloat16*)a.val_cache, (const float*)a.cos_sin,
+                     (const int*)a.positions, (const int*)a.slot_mapping,
+                     a.num_q_heads, a.num_kv_heads, a.head_dim, a.page_size,
+                     a.q_stride, a.kv_stride);
+  return hipGetLastError();
 }
 
 }  // extern "C"

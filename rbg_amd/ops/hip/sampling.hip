@@ -22,6 +22,7 @@
 // parameters, and every cross-thread combine is an integer max or add: the
 // result is independent of batch position, batch size and arrival order.
 #include "common.h"
+#include "launch.h"
 
 #include <math.h>
 
@@ -422,15 +423,17 @@ sample_kernel(int64_t* __restrict__ out_tok, int* __restrict__ out_kept,
 extern "C" {
 
 // One workgroup per row; all per-row parameters are device arrays of n.
-void launch_sample(void* out_tok, void* out_kept, const void* logits,
-                   const void* temperature, const void* top_k,
-                   const void* top_p, const void* min_p, const void* seed,
-                   const void* pos, int n, int V, hipStream_t stream) {
+hipError_t launch_sample(void* out_tok, void* out_kept, const void* logits,
+                         const void* temperature, const void* top_k,
+                         const void* top_p, const void* min_p,
+                         const void* seed, const void* pos, int n, int V,
+                         hipStream_t stream) {
   hipLaunchKernelGGL(sample_kernel, dim3(n), dim3(NT), 0, stream,
                      (int64_t*)out_tok, (int*)out_kept, (const float*)logits,
                      (const float*)temperature, (const int*)top_k,
                      (const float*)top_p, (const float*)min_p,
                      (const int64_t*)seed, (const int*)pos, V);
+  return hipGetLastError();
 }
 
 }  // extern "C"

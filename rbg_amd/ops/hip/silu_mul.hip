@@ -2,6 +2,7 @@
 // Pure HBM-bound elementwise op — grid-stride, 16-byte bf16 vectors
 // (guide Appendix B elementwise pattern).
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -31,8 +32,8 @@ __global__ void silu_mul_kernel(__hip_bfloat16* __restrict__ out,   // [T, I]
 
 extern "C" {
 
-void launch_silu_mul(void* out, const void* x, int tokens, int inter,
-                     hipStream_t stream) {
+hipError_t launch_silu_mul(void* out, const void* x, int tokens, int inter,
+                           hipStream_t stream) {
   const long total_vec = (long)tokens * (inter / 8);
   int blocks = (int)((total_vec + 255) / 256);
   if (blocks > 8192) blocks = 8192;   // grid-stride covers the rest
@@ -40,6 +41,7 @@ void launch_silu_mul(void* out, const void* x, int tokens, int inter,
   hipLaunchKernelGGL(silu_mul_kernel, dim3(blocks), dim3(256), 0, stream,
                      (__hip_bfloat16*)out, (const __hip_bfloat16*)x, inter,
                      total_vec);
+  return hipGetLastError();
 }
 
 }  // extern "C"

@@ -38,6 +38,7 @@
 // M <= 128, N % 64 == 0 where it measured faster (bindings.cpp).  This
 // kernel stays for N % 64 != 0 and M > 128.
 #include "common.h"
+#include "launch.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 gg_bf8;
 
@@ -443,75 +444,69 @@ __global__ void reduce_splits_kernel(const float* __restrict__ ws,
 // ---------------------------------------------------------------------------
 // C launchers (torch glue lives in bindings.cpp)
 
-extern "C" void launch_skinny_gemm(void* c, void* ws, const void* a,
-                                   const void* w, int M, int N, int K,
-                                   int splits, hipStream_t stream) {
+// One kernel per split count the GEMMs are instantiated for.
+#define LAUNCH_SPLITS(KERNEL, MT)                                            \
+  switch (splits) {                                                          \
+    case 1:                                                                  \
+      KERNEL<MT, 1><<<grid, block, 0, stream>>>(ap, wp, cp, nullptr, M, N,   \
+                                                K);                          \
+      break;                                                                 \
+    case 2:                                                                  \
+      KERNEL<MT, 2><<<grid, block, 0, stream>>>(ap, wp, cp, wsp, M, N, K);   \
+      break;                                                                 \
+    case 4:                                                                  \
+      KERNEL<MT, 4><<<grid, block, 0, stream>>>(ap, wp, cp, wsp, M, N, K);   \
+      break;                                                                 \
+    case 8:                                                                  \
+      KERNEL<MT, 8><<<grid, block, 0, stream>>>(ap, wp, cp, wsp, M, N, K);   \
+      break;                                                                 \
+    default:                                                                 \
+      return hipErrorInvalidValue;                                           \
+  }
+
+// M <= 256 and N % 32 == 0
+extern "C" hipError_t launch_skinny_gemm(void* c, void* ws, const void* a,
+                                         const void* w, int M, int N, int K,
+                                         int splits, hipStream_t stream) {
   const dim3 grid((N >> 5) * splits), block(SG_NT);
   const __hip_bfloat16* ap = (const __hip_bfloat16*)a;
   const __hip_bfloat16* wp = (const __hip_bfloat16*)w;
   __hip_bfloat16* cp = (__hip_bfloat16*)c;
   float* wsp = (float*)ws;
   const int m_tiles = (M + 15) >> 4;
-
-#define LAUNCH_MT(MT)                                                        \
-  do {                                                                       \
-    if (splits == 1)                                                         \
-      skinny_gemm_kernel<MT, 1><<<grid, block, 0, stream>>>(                 \
-          ap, wp, cp, nullptr, M, N, K);                                     \
-    else if (splits == 2)                                                    \
-      skinny_gemm_kernel<MT, 2><<<grid, block, 0, stream>>>(                 \
-          ap, wp, cp, wsp, M, N, K);                                         \
-    else if (splits == 4)                                                    \
-      skinny_gemm_kernel<MT, 4><<<grid, block, 0, stream>>>(                 \
-          ap, wp, cp, wsp, M, N, K);                                         \
-    else                                                                     \
-      skinny_gemm_kernel<MT, 8><<<grid, block, 0, stream>>>(                 \
-          ap, wp, cp, wsp, M, N, K);                                         \
-  } while (0)
-
-  if (m_tiles <= 1) LAUNCH_MT(1);
-  else if (m_tiles <= 2) LAUNCH_MT(2);
-  else if (m_tiles <= 4) LAUNCH_MT(4);
-  else if (m_tiles <= 8) LAUNCH_MT(8);
-  else LAUNCH_MT(16);
-#undef LAUNCH_MT
+  if (m_tiles < 1) return hipErrorInvalidValue;
+  if (m_tiles <= 1) LAUNCH_SPLITS(skinny_gemm_kernel, 1)
+  else if (m_tiles <= 2) LAUNCH_SPLITS(skinny_gemm_kernel, 2)
+  else if (m_tiles <= 4) LAUNCH_SPLITS(skinny_gemm_kernel, 4)
+  else if (m_tiles <= 8) LAUNCH_SPLITS(skinny_gemm_kernel, 8)
+  else if (m_tiles <= 16) LAUNCH_SPLITS(skinny_gemm_kernel, 16)
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
 }
 
-// M <= 128 and N % 64 == 0 (checked in bindings.cpp)
-extern "C" void launch_skinny_gemm_wide(void* c, void* ws, const void* a,
-                                        const void* w, int M, int N, int K,
-                                        int splits, hipStream_t stream) {
+// M <= 128 and N % 64 == 0
+extern "C" hipError_t launch_skinny_gemm_wide(void* c, void* ws, const void* a,
+                                              const void* w, int M, int N,
+                                              int K, int splits,
+                                              hipStream_t stream) {
   const dim3 grid((N >> 6) * splits), block(SGW_NT);
   const __hip_bfloat16* ap = (const __hip_bfloat16*)a;
   const __hip_bfloat16* wp = (const __hip_bfloat16*)w;
   __hip_bfloat16* cp = (__hip_bfloat16*)c;
   float* wsp = (float*)ws;
-
-#define LAUNCH_MTW(MTW)                                                      \
-  do {                                                                       \
-    if (splits == 1)                                                         \
-      skinny_gemm_wide_kernel<MTW, 1><<<grid, block, 0, stream>>>(           \
-          ap, wp, cp, nullptr, M, N, K);                                     \
-    else if (splits == 2)                                                    \
-      skinny_gemm_wide_kernel<MTW, 2><<<grid, block, 0, stream>>>(           \
-          ap, wp, cp, wsp, M, N, K);                                         \
-    else if (splits == 4)                                                    \
-      skinny_gemm_wide_kernel<MTW, 4><<<grid, block, 0, stream>>>(           \
-          ap, wp, cp, wsp, M, N, K);                                         \
-    else                                                                     \
-      skinny_gemm_wide_kernel<MTW, 8><<<grid, block, 0, stream>>>(           \
-          ap, wp, cp, wsp, M, N, K);                                         \
-  } while (0)
-
-  if (M <= 64) LAUNCH_MTW(1);
-  else LAUNCH_MTW(2);
-#undef LAUNCH_MTW
+  if (M < 1) return hipErrorInvalidValue;
+  if (M <= 64) LAUNCH_SPLITS(skinny_gemm_wide_kernel, 1)
+  else if (M <= 128) LAUNCH_SPLITS(skinny_gemm_wide_kernel, 2)
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
 }
+#undef LAUNCH_SPLITS
 
-extern "C" void launch_reduce_splits(void* c, const void* ws, int splits,
-                                     long mn, hipStream_t stream) {
+extern "C" hipError_t launch_reduce_splits(void* c, const void* ws, int splits,
+                                           long mn, hipStream_t stream) {
   const int threads = 256;
   reduce_splits_kernel<<<dim3((mn + threads - 1) / threads), dim3(threads),
                          0, stream>>>((const float*)ws, (__hip_bfloat16*)c,
                                       splits, mn);
+  return hipGetLastError();
 }

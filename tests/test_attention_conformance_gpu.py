@@ -258,10 +258,14 @@ def _mutations():
     def block_tables_not_contiguous(a, dev):
         a["bt"] = torch.ones(3, 8, dtype=torch.int32, device=dev)[:, ::2]
 
+    def value_cache_on_cpu(a, dev):
+        a["vc"] = a["vc"].cpu()
+
     return [page_not_pow2, cache_not_contiguous, value_cache_not_contiguous,
             cache_not_bf16, cache_head_dim_64, cache_shapes_differ,
             heads_not_divisible, block_tables_on_cpu, context_lens_on_cpu,
-            block_tables_rows, context_lens_rows, block_tables_not_contiguous]
+            block_tables_rows, context_lens_rows, block_tables_not_contiguous,
+            value_cache_on_cpu]
 
 
 @pytest.mark.parametrize("mutate", _mutations(), ids=lambda f: f.__name__)
@@ -332,9 +336,19 @@ def _rope_mutations():
     def slots_too_few(a, dev):
         a["slots"] = a["slots"][:3].contiguous()
 
+    def value_cache_on_cpu(a, dev):
+        a["vc"] = a["vc"].cpu()
+
+    def v_at_2_byte_offset(a, dev):
+        # the kernel reads V rows as 16-byte vectors
+        n = a["v"].numel()
+        flat = torch.zeros(n + 8, dtype=torch.bfloat16, device=dev)
+        a["v"] = flat[1:n + 1].view(a["v"].shape)
+
     return [page_not_pow2, cache_not_contiguous, cache_not_bf16,
             cache_head_dim_64, cache_kv_heads_differ, slots_on_cpu,
-            positions_on_cpu, slots_too_few]
+            positions_on_cpu, slots_too_few, value_cache_on_cpu,
+            v_at_2_byte_offset]
 
 
 @pytest.mark.parametrize("mutate", _rope_mutations(),
@@ -344,3 +358,104 @@ def test_rope_store_rejects_bad_input(dev, mutate):
     mutate(a, dev)
     with pytest.raises(RuntimeError):
         _rope(a)
+
+
+_PREFILL_GOOD = ac.PrefillCase(8, 2, ((63, 63), (65, 65)))
+
+
+def _good_prefill_args(dev):
+    """The arguments ops.prefill_attention hands the extension for QH 8,
+    KVH 2 and lengths 63 and 65."""
+    data, d = _on_dev("prefill", _PREFILL_GOOD, "scaled", dev)
+    qtile = 128 if (ops.PREFILL_SWZ & 12) else 64
+    info, lens = ops.reference.prefill_block_info(d["cu_q"].cpu(), qtile=qtile)
+    return data, dict(q=d["q"], k=d["k"], v=d["v"], info=info.to(dev),
+                      lens=lens.to(dev))
+
+
+def _prefill(a):
+    return ops._hip.prefill_attention(a["q"], a["k"], a["v"], a["info"],
+                                      a["lens"], ac.SCALE, ops.PREFILL_SWZ)
+
+
+def test_prefill_accepts_the_baseline_arguments(dev):
+    data, a = _good_prefill_args(dev)
+    ok, msg, _ = ac.check(_prefill(a), data)
+    assert ok, msg
+
+
+def test_prefill_empty_batch(dev):
+    _, a = _good_prefill_args(dev)
+    for name in ("q", "k", "v", "info", "lens"):
+        a[name] = a[name][:0]
+    assert _prefill(a).shape == (0, 8, 128)
+
+
+def _prefill_mutations():
+    def block_info_not_int32(a, dev):
+        a["info"] = a["info"].long()
+
+    def seq_lens_not_int32(a, dev):
+        a["lens"] = a["lens"].long()
+
+    def block_info_on_cpu(a, dev):
+        a["info"] = a["info"].cpu()
+
+    def seq_lens_on_cpu(a, dev):
+        a["lens"] = a["lens"].cpu()
+
+    def block_info_not_contiguous(a, dev):
+        wide = torch.zeros(a["info"].size(0), 8, dtype=torch.int32, device=dev)
+        wide[:, :4] = a["info"]
+        a["info"] = wide[:, :4]
+
+    def seq_lens_not_contiguous(a, dev):
+        a["lens"] = a["lens"].repeat_interleave(2)[::2]
+
+    def block_info_flat(a, dev):
+        a["info"] = a["info"].reshape(-1)
+
+    def block_info_three_columns(a, dev):
+        a["info"] = a["info"][:, :3].contiguous()
+
+    def block_info_more_rows_than_seq_lens(a, dev):
+        a["info"] = torch.cat([a["info"], a["info"][-1:]])
+
+    def kv_shapes_differ(a, dev):
+        a["v"] = a["v"][:-1]
+
+    def v_not_row_sliced(a, dev):
+        a["v"] = a["v"].transpose(0, 1).contiguous().transpose(0, 1)
+
+    def q_head_dim_64(a, dev):
+        a["q"] = a["q"][:, :, :64].contiguous()
+
+    def kv_head_dim_64(a, dev):
+        a["k"] = a["k"][:, :, :64].contiguous()
+        a["v"] = a["v"][:, :, :64].contiguous()
+
+    def heads_not_divisible(a, dev):
+        a["q"] = a["q"][:, :7].contiguous()
+
+    def no_kv_heads(a, dev):
+        a["k"] = a["k"][:, :0]
+        a["v"] = a["v"][:, :0]
+
+    def v_on_cpu(a, dev):
+        a["v"] = a["v"].cpu()
+
+    return [block_info_not_int32, seq_lens_not_int32, block_info_on_cpu,
+            seq_lens_on_cpu, block_info_not_contiguous,
+            seq_lens_not_contiguous, block_info_flat,
+            block_info_three_columns, block_info_more_rows_than_seq_lens,
+            kv_shapes_differ, v_not_row_sliced, q_head_dim_64,
+            kv_head_dim_64, heads_not_divisible, no_kv_heads, v_on_cpu]
+
+
+@pytest.mark.parametrize("mutate", _prefill_mutations(),
+                         ids=lambda f: f.__name__)
+def test_prefill_rejects_bad_input(dev, mutate):
+    _, a = _good_prefill_args(dev)
+    mutate(a, dev)
+    with pytest.raises(RuntimeError):
+        _prefill(a)
