@@ -14,6 +14,7 @@ from dataclasses import dataclass, field
 
 KV_CACHE_DTYPES = ("bf16", "fp8_e4m3")
 KV_SCALE_LOG2_MIN, KV_SCALE_LOG2_MAX = -16, 16
+PREFILL_KV_READS = ("gather", "paged")
 
 
 def kv_element_size(kv_cache_dtype: str) -> int:
@@ -117,8 +118,20 @@ class EngineConfig:
     kv_cache_dtype: str = "bf16"
     kv_k_scale_log2: int = 0
     kv_v_scale_log2: int = 0
+    # How a prefill step with a past (or any step of an fp8 pool) reads the
+    # cached K/V (docs/FEATURES.md "Paged prefill"): "gather" copies the
+    # history into contiguous rows first, "paged" hands the pool and the
+    # block tables to the attention kernel
+    prefill_kv_read: str = "gather"
 
     def __post_init__(self) -> None:
+        if self.prefill_kv_read not in PREFILL_KV_READS:
+            raise ValueError("unknown prefill_kv_read %r (one of %s)" % (
+                self.prefill_kv_read, ", ".join(PREFILL_KV_READS)))
+        if self.prefill_kv_read == "paged" and (
+                self.page_size != 16 or self.model.head_dim != 128):
+            raise ValueError("prefill_kv_read 'paged' needs page_size 16 and "
+                             "head_dim 128")
         kv_element_size(self.kv_cache_dtype)       # raises on an unknown name
         for name in ("kv_k_scale_log2", "kv_v_scale_log2"):
             e = getattr(self, name)

@@ -15,6 +15,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
+from .. import ops
 from ..models.llama import (ForwardBatch, LlamaForCausalLM, PPContext,
                             TPContext)
 from .config import EngineConfig
@@ -70,6 +71,9 @@ class ModelRunner:
         # chunked or whole prefill)
         any_past = (any(seq.num_prefilled > 0 for seq in seqs) or
                     self.cache.fp8)
+        # prefill_kv_read "paged": such a step hands the attention kernel the
+        # block tables instead of one gather slot per key of every history
+        paged = any_past and self.cfg.prefill_kv_read == "paged"
         for seq in seqs:
             start = seq.num_prefilled
             end = start + (seq.chunk_len or
@@ -79,7 +83,7 @@ class ModelRunner:
             slots.extend(seq.block_table.slots_for(start, end - start))
             cu.append(cu[-1] + (end - start))
             cu_k.append(cu_k[-1] + end)
-            if any_past:
+            if any_past and not paged:
                 gather.extend(seq.block_table.slots_for(0, end))
             if end == seq.num_prompt_tokens:
                 completing.append(seq)
@@ -91,7 +95,20 @@ class ModelRunner:
             slot_mapping=self._i32(slots),
             cu_seqlens=self._i32(cu),
             cu_seqlens_k=self._i32(cu_k) if any_past else None,
-            kv_gather_slots=self._i32(gather) if any_past else None)
+            kv_gather_slots=(self._i32(gather) if any_past and not paged
+                             else None))
+        if paged:
+            # the table and the kernel's block map, once per step and from
+            # the host lists: no layer reads anything back from the device
+            ps = self.cfg.page_size
+            npages = [(cu_k[b + 1] - cu_k[b] + ps - 1) // ps
+                      for b in range(len(seqs))]
+            width = max(npages)
+            batch.prefill_block_tables = self._i32(
+                [seq.block_table.pages[:n] + [0] * (width - n)
+                 for seq, n in zip(seqs, npages)])
+            batch.prefill_block_map = ops.prefill_paged_block_map(
+                cu, cu_k, width, self.device)
         hidden_in = None
         if not self.pp.first:
             hidden_in = self.pp.recv_prev(

@@ -59,6 +59,7 @@ def _engine_cfg(ctx: WorkerContext) -> EngineConfig:
         kv_cache_dtype=str(args.get("kv_cache_dtype", "bf16")),
         kv_k_scale_log2=int(args.get("kv_k_scale_log2", 0)),
         kv_v_scale_log2=int(args.get("kv_v_scale_log2", 0)),
+        prefill_kv_read=str(args.get("prefill_kv_read", "gather")),
     )
 
 

@@ -40,6 +40,10 @@ class ForwardBatch:
     kv_gather_slots: Optional[torch.Tensor] = None  # [Tkv] int32 — prefix
     #   caching / chunked prefill: gather the FULL [past; new] K/V from the
     #   paged pool (the new tokens' rows were just written by rope_store_kv)
+    # EngineConfig.prefill_kv_read == "paged": the attention kernel reads
+    # the pool itself through these instead of kv_gather_slots
+    prefill_block_tables: Optional[torch.Tensor] = None  # [B, pages] int32
+    prefill_block_map: Optional[tuple] = None   # ops.prefill_paged_block_map
     # decode
     block_tables: Optional[torch.Tensor] = None  # [S, max_pages] int32
     context_lens: Optional[torch.Tensor] = None  # [S] int32
@@ -227,7 +231,14 @@ class LlamaAttention(nn.Module):
                               batch.positions, batch.slot_mapping)
         q3 = q.view(T, self.heads, self.head_dim)
         if batch.mode == "prefill":
-            if fp8:
+            if batch.prefill_block_tables is not None:
+                # this step's keys were just written to the pool above
+                o = ops.prefill_attention_paged(
+                    q3, key_cache, value_cache, batch.prefill_block_tables,
+                    batch.cu_seqlens, self.scale, batch.cu_seqlens_k,
+                    kv.k_scale_log2, kv.v_scale_log2,
+                    block_map=batch.prefill_block_map)
+            elif fp8:
                 # every key, this step's included, is read back dequantised
                 if batch.kv_gather_slots is None:
                     raise RuntimeError("an fp8 KV pool prefills through the "

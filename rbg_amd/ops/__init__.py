@@ -9,6 +9,7 @@ as the implementation.
 from __future__ import annotations
 
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -259,6 +260,96 @@ def prefill_attention(q, k, v, cu_seqlens, scale: float,
             PREFILL_SWZ)
     return reference.prefill_attention(q, k, v, cu_seqlens, scale,
                                        cu_seqlens_k)
+
+
+PAGED_PREFILL_QTILE = 128      # q rows per workgroup of the paged kernel
+
+
+class PagedBlockMap(NamedTuple):
+    """The paged prefill kernel's block map and what it was checked against:
+    it indexes rows [0, num_seqs) of a table at least table_width wide."""
+    block_info: torch.Tensor
+    seq_lens: torch.Tensor
+    num_seqs: int
+    table_width: int
+
+
+def prefill_paged_block_map(cu_seqlens, cu_seqlens_k, table_width: int,
+                            device):
+    """(block_info, seq_lens) of ops.prefill_attention_paged on `device`,
+    from HOST lists (or CPU tensors) of cumulative q and KV lengths.  Raises
+    ValueError where the kernel would read outside a sequence's table row."""
+    cu = reference._int_list(cu_seqlens)
+    cuk = cu if cu_seqlens_k is None else reference._int_list(cu_seqlens_k)
+    if len(cu) != len(cuk):
+        raise ValueError("cu_seqlens has %d entries but cu_seqlens_k has %d"
+                         % (len(cu), len(cuk)))
+    for b in range(len(cu) - 1):
+        Lq, Lk = cu[b + 1] - cu[b], cuk[b + 1] - cuk[b]
+        if Lq < 0 or Lk < Lq:
+            raise ValueError("sequence %d has %d q rows but %d keys"
+                             % (b, Lq, Lk))
+        if (Lk + 15) // 16 > table_width:
+            raise ValueError("sequence %d needs %d block-table columns, the "
+                             "table has %d" % (b, (Lk + 15) // 16,
+                                               table_width))
+    block_info, seq_lens = reference.prefill_block_info_paged(
+        cu, PAGED_PREFILL_QTILE, cuk, device=device)
+    return PagedBlockMap(block_info, seq_lens, len(cu) - 1, table_width)
+
+
+def prefill_attention_paged(q, key_cache, value_cache, block_tables,
+                            cu_seqlens, scale: float, cu_seqlens_k=None,
+                            k_scale_log2: int = 0, v_scale_log2: int = 0,
+                            block_map=None) -> torch.Tensor:
+    """Varlen causal prefill attention that reads K and V in place from the
+    paged pool (bf16 or e4m3, 16-token pages, head_dim 128) through
+    block_tables [num_seqs, max_pages]: sequence b's q rows are the LAST Lq
+    positions of its Lk keys (docs/FEATURES.md "Paged prefill").  An e4m3
+    pool is read as e4m3 * 2^e; the exponents are ignored for bf16.
+
+    block_map = prefill_paged_block_map(...) lets a caller that has the
+    lengths on the host build (and check) the map once per step; without it
+    the op reads cu_seqlens back and builds it itself.  A PagedBlockMap is
+    checked against block_tables' shape here.  A bare (block_info, seq_lens)
+    pair is taken on trust: the caller vouches that every sequence index in
+    it is a row of block_tables and that every sequence's pages fit the
+    table's width, which nothing below this function can check."""
+    fp8 = _is_fp8_pair(key_cache, value_cache)
+    if fp8:
+        check_kv_scale_log2(k_scale_log2, "kv_k_scale_log2")
+        check_kv_scale_log2(v_scale_log2, "kv_v_scale_log2")
+    else:
+        k_scale_log2 = v_scale_log2 = 0
+    if key_cache.dim() != 4 or key_cache.shape[2] != 16 or \
+            key_cache.shape[3] != 128:
+        raise ValueError("paged prefill needs caches [pages, KVH, 16, 128], "
+                         "got %s" % (tuple(key_cache.shape),))
+    if block_tables.dim() != 2 or block_tables.dtype != torch.int32:
+        raise ValueError("block_tables must be int32 [num_seqs, max_pages]")
+    if block_map is None:
+        cu = cu_seqlens.cpu()
+        cuk = None if cu_seqlens_k is None else cu_seqlens_k.cpu()
+        if cu.numel() - 1 > block_tables.shape[0]:
+            raise ValueError("%d sequences but %d block-table rows" % (
+                cu.numel() - 1, block_tables.shape[0]))
+        block_map = prefill_paged_block_map(cu, cuk, block_tables.shape[1],
+                                            q.device)
+    if isinstance(block_map, PagedBlockMap) and (
+            block_map.num_seqs > block_tables.shape[0] or
+            block_map.table_width > block_tables.shape[1]):
+        raise ValueError("block_map was built for %d sequences and a table "
+                         "%d wide, block_tables is %s" % (
+                             block_map.num_seqs, block_map.table_width,
+                             tuple(block_tables.shape)))
+    if not _on_gpu(q):
+        return reference.prefill_attention_paged(
+            q, key_cache, value_cache, block_tables, cu_seqlens, scale,
+            cu_seqlens_k, k_scale_log2, v_scale_log2)
+    block_info, seq_lens = block_map[0], block_map[1]
+    return _require_hip().prefill_attention_paged(
+        q, key_cache, value_cache, block_tables, block_info, seq_lens, scale,
+        k_scale_log2, v_scale_log2)
 
 
 build_cos_sin_table = reference.build_cos_sin_table

@@ -430,6 +430,77 @@ torch::Tensor prefill_attention(torch::Tensor q, torch::Tensor k,
   return out;
 }
 
+// Prefill over the paged pool itself (attn_prefill_paged.hip).  block_info and
+// seq_lens are reference.prefill_block_info_paged's map (qtile 128): the
+// caller vouches that every sequence index is a row of block_tables and that
+// the table is ceil(seq_len / 16) columns wide (ops.prefill_attention_paged
+// checks both on the host); the exponents are ignored for a bf16 pool.
+torch::Tensor prefill_attention_paged(torch::Tensor q, torch::Tensor key_cache,
+                                      torch::Tensor value_cache,
+                                      torch::Tensor block_tables,
+                                      torch::Tensor block_info,
+                                      torch::Tensor seq_lens, double scale,
+                                      int64_t k_scale_log2,
+                                      int64_t v_scale_log2) {
+  check_bf16_rowslice(q, "q");
+  TORCH_CHECK(q.size(2) == 128, "head_dim must be 128");
+  const auto cache_dtype = key_cache.scalar_type();
+  TORCH_CHECK(cache_dtype == torch::kBFloat16 ||
+                  cache_dtype == torch::kFloat8_e4m3fn,
+              "key_cache must be bf16 or float8_e4m3fn");
+  const bool fp8 = cache_dtype == torch::kFloat8_e4m3fn;
+  check_kv_caches(key_cache, value_cache, cache_dtype);
+  TORCH_CHECK(key_cache.device() == q.device(), "q/cache device mismatch");
+  TORCH_CHECK(key_cache.size(2) == 16 && key_cache.size(3) == 128,
+              "paged prefill needs a page size of 16 and head_dim 128");
+  const int64_t num_q_heads = q.size(1), num_kv_heads = key_cache.size(1);
+  TORCH_CHECK(num_kv_heads >= 1 && num_q_heads % num_kv_heads == 0,
+              "q heads must be a multiple of the (>= 1) KV heads");
+  check_i32_gpu(block_tables, "block_tables");
+  check_i32_gpu(block_info, "block_info");
+  check_i32_gpu(seq_lens, "seq_lens");
+  TORCH_CHECK(block_tables.device() == q.device() &&
+                  block_info.device() == q.device() &&
+                  seq_lens.device() == q.device(),
+              "block_tables, block_info and seq_lens must be on q's device");
+  TORCH_CHECK(block_tables.dim() == 2,
+              "block_tables must be [num_seqs, max_pages]");
+  TORCH_CHECK(block_info.dim() == 2 && block_info.size(1) == 4,
+              "block_info must be [nblocks, 4]");
+  const int64_t nblocks = block_info.size(0);
+  TORCH_CHECK(seq_lens.dim() == 1 && seq_lens.size(0) == nblocks,
+              "seq_lens must be [nblocks]");
+  TORCH_CHECK(nblocks * num_q_heads <= INT32_MAX, "too many blocks");
+  const float k_scale =
+      fp8 ? check_scale_log2(k_scale_log2, "kv_k_scale_log2") : 1.f;
+  const float v_scale =
+      fp8 ? check_scale_log2(v_scale_log2, "kv_v_scale_log2") : 1.f;
+  auto out = torch::empty({q.size(0), num_q_heads, 128}, q.options());
+  if (q.size(0) == 0 || nblocks == 0) return out;
+  TORCH_CHECK(block_tables.size(0) >= 1 && block_tables.size(1) >= 1,
+              "block_tables is empty but there are blocks to run");
+  PrefillPagedLaunch a;
+  a.out = out.data_ptr();
+  a.q = q.data_ptr();
+  a.key_cache = key_cache.data_ptr();
+  a.val_cache = value_cache.data_ptr();
+  a.block_tables = block_tables.data_ptr();
+  a.block_info = block_info.data_ptr();
+  a.seq_lens = seq_lens.data_ptr();
+  // 2^ek folds into the score scale: a power of two, so the product is exact
+  a.scale = (float)scale * k_scale;
+  a.v_scale = v_scale;
+  a.nblocks = (int)nblocks;
+  a.num_seqs = (int)block_tables.size(0);
+  a.max_pages = (int)block_tables.size(1);
+  a.num_q_heads = (int)num_q_heads;
+  a.num_kv_heads = (int)num_kv_heads;
+  a.q_stride = (int)q.stride(0);
+  a.fp8 = fp8;
+  LAUNCH(launch_prefill_attention_paged, a, current_stream());
+  return out;
+}
+
 torch::Tensor mfma_probe(torch::Tensor a, torch::Tensor b, int64_t a_split,
                          int64_t b_split) {
   auto d = torch::zeros({16, 16}, a.options().dtype(torch::kFloat32));
@@ -809,6 +880,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("num_splits"), py::arg("k_scale_log2"),
         py::arg("v_scale_log2"), py::arg("combine") = 0);
   m.def("prefill_attention", &prefill_attention, "varlen causal flash prefill");
+  m.def("prefill_attention_paged", &prefill_attention_paged,
+        "varlen causal flash prefill reading K/V through the block table "
+        "(bf16 or e4m3 pool)");
   m.def("mfma_probe", &mfma_probe, "MFMA layout probe");
   m.def("mfma_probe32", &mfma_probe32, "32x32x16 MFMA layout probe");
   m.def("skinny_gemm", &skinny_gemm, "decode-shape GEMM (M<=128)",

@@ -70,6 +70,27 @@ struct PrefillLaunch {
   int kv_stride;
 };
 
+// Prefill that reads K/V in place from the paged pool (16-token pages,
+// head_dim 128); fp8 picks the e4m3 instantiation.
+struct PrefillPagedLaunch {
+  void* out;                 // [T, QH, 128] bf16
+  const void* q;             // [T, QH, 128] bf16, rows q_stride apart
+  const void* key_cache;     // [pages, KVH, 16, 128] bf16 or e4m3
+  const void* val_cache;
+  const void* block_tables;  // [num_seqs, max_pages] int32
+  const void* block_info;    // [nblocks, 4] int32, column 2 = sequence index
+  const void* seq_lens;      // [nblocks] int32
+  float scale;               // softmax scale (times 2^ek for e4m3)
+  float v_scale;             // 2^ev, e4m3 only
+  int nblocks;
+  int num_seqs;              // rows of block_tables: the kernel clamps to them
+  int max_pages;
+  int num_q_heads;
+  int num_kv_heads;
+  int q_stride;
+  bool fp8;
+};
+
 // Strides and chunk_vec count 16-byte vectors.
 struct KvPeerCopyLaunch {
   void* dst_base;            // peer-mapped pool
@@ -114,6 +135,8 @@ hipError_t launch_decode_attention_fp8(const DecodeLaunch& a, float v_scale,
                                        hipStream_t stream);
 hipError_t launch_prefill_attention(const PrefillLaunch& a,
                                     hipStream_t stream);
+hipError_t launch_prefill_attention_paged(const PrefillPagedLaunch& a,
+                                          hipStream_t stream);
 
 hipError_t launch_mfma_probe(void* d, const void* a, const void* b,
                              int a_split, int b_split, hipStream_t stream);

@@ -221,6 +221,69 @@ def prefill_block_info(cu_seqlens: torch.Tensor, qtile: int = 64,
             torch.tensor(lens, dtype=torch.int32, device=device))
 
 
+def _int_list(x) -> list:
+    return x.tolist() if isinstance(x, torch.Tensor) else list(x)
+
+
+def prefill_block_info_paged(cu_seqlens, qtile: int = 128, cu_seqlens_k=None,
+                             device=None
+                             ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Block map of the paged prefill kernel: prefill_block_info with the
+    sequence's index (its block-table row) where kv_start_row was.  Takes
+    tensors or plain host lists, so a caller that has the lists builds the
+    map without reading anything back from the device."""
+    cu = _int_list(cu_seqlens)
+    cuk = _int_list(cu_seqlens_k) if cu_seqlens_k is not None else cu
+    infos = []
+    lens = []
+    for b in range(len(cu) - 1):
+        Lq, Lk = cu[b + 1] - cu[b], cuk[b + 1] - cuk[b]
+        for qb in range((Lq + qtile - 1) // qtile):
+            infos.append((cu[b], qb, b, Lk - Lq))
+            lens.append(Lk)
+    if device is None and isinstance(cu_seqlens, torch.Tensor):
+        device = cu_seqlens.device
+    return (torch.tensor(infos, dtype=torch.int32, device=device).view(-1, 4),
+            torch.tensor(lens, dtype=torch.int32, device=device))
+
+
+def paged_kv_slots(block_tables: torch.Tensor, seq_lens, page_size: int
+                   ) -> torch.Tensor:
+    """Slots of keys 0 .. L-1 of every sequence, in order, read through its
+    block-table row: int32 [sum L] on the table's device."""
+    out = []
+    for b, L in enumerate(_int_list(seq_lens)):
+        pos = torch.arange(L, device=block_tables.device)
+        pages = block_tables[b, :(L + page_size - 1) // page_size].long()
+        out.append(pages[pos // page_size] * page_size + pos % page_size)
+    if not out:
+        return torch.zeros(0, dtype=torch.int32, device=block_tables.device)
+    return torch.cat(out).to(torch.int32)
+
+
+def prefill_attention_paged(q, key_cache, value_cache, block_tables,
+                            cu_seqlens, scale: float, cu_seqlens_k=None,
+                            k_scale_log2: int = 0, v_scale_log2: int = 0
+                            ) -> torch.Tensor:
+    """Prefill attention over the paged pool: the keys are gathered through
+    the block tables (dequantised for an e4m3 pool), then prefill_attention."""
+    cuk = _int_list(cu_seqlens_k if cu_seqlens_k is not None else cu_seqlens)
+    page_size = key_cache.shape[2]
+    slots = paged_kv_slots(block_tables,
+                           [cuk[b + 1] - cuk[b] for b in range(len(cuk) - 1)],
+                           page_size)
+    if key_cache.dtype == torch.float8_e4m3fn:
+        k_full = kv_gather_dequant(key_cache, slots, k_scale_log2)
+        v_full = kv_gather_dequant(value_cache, slots, v_scale_log2)
+    else:
+        sl = slots.long()
+        pages, offs = sl // page_size, sl % page_size
+        k_full = key_cache[pages, :, offs]
+        v_full = value_cache[pages, :, offs]
+    cu_k = torch.tensor(cuk, dtype=torch.int32, device=q.device)
+    return prefill_attention(q, k_full, v_full, cu_seqlens, scale, cu_k)
+
+
 # ---------------------------------------------------------------------------
 # seeded sampling (docs/FEATURES.md "Seeded sampling"; hip/sampling.hip)
 # ---------------------------------------------------------------------------

@@ -22,6 +22,7 @@ HIP_DIR = os.path.join(ROOT, "rbg_amd", "ops", "hip")
 HIP_SOURCES = [
     "attn_decode.hip",
     "attn_prefill.hip",
+    "attn_prefill_paged.hip",
     "mfma_probe.hip",
     "rmsnorm.hip",
     "rope_kv.hip",
