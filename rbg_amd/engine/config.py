@@ -15,6 +15,7 @@ from dataclasses import dataclass, field
 KV_CACHE_DTYPES = ("bf16", "fp8_e4m3")
 KV_SCALE_LOG2_MIN, KV_SCALE_LOG2_MAX = -16, 16
 PREFILL_KV_READS = ("gather", "paged")
+WEIGHT_DTYPES = ("bf16", "fp8_e4m3")
 
 
 def kv_element_size(kv_cache_dtype: str) -> int:
@@ -123,8 +124,15 @@ class EngineConfig:
     # history into contiguous rows first, "paged" hands the pool and the
     # block tables to the attention kernel
     prefill_kv_read: str = "gather"
+    # Projection weights (docs/FEATURES.md "FP8 weights"): "fp8_e4m3" holds
+    # qkv, o, gate_up and down of every layer as e4m3 bytes with one
+    # power-of-two exponent per output row
+    weight_dtype: str = "bf16"
 
     def __post_init__(self) -> None:
+        if self.weight_dtype not in WEIGHT_DTYPES:
+            raise ValueError("unknown weight_dtype %r (one of %s)" % (
+                self.weight_dtype, ", ".join(WEIGHT_DTYPES)))
         if self.prefill_kv_read not in PREFILL_KV_READS:
             raise ValueError("unknown prefill_kv_read %r (one of %s)" % (
                 self.prefill_kv_read, ", ".join(PREFILL_KV_READS)))

@@ -34,15 +34,17 @@ class ModelRunner:
         self.device = torch.device(cfg.device)
         torch.manual_seed(cfg.seed)
         self.pp = pp or PPContext()
-        self.model = LlamaForCausalLM(cfg.model, self.device, tp, pp=self.pp)
+        self.model = LlamaForCausalLM(cfg.model, self.device, tp, pp=self.pp,
+                                      weight_dtype=cfg.weight_dtype)
         self.cache = PagedKVCache(cfg, self.device,
                                   num_layers=self.model.num_local_layers)
         self.max_pages_per_seq = (cfg.max_seq_len + cfg.page_size - 1) // \
             cfg.page_size
         self._graphs: Dict[int, Tuple] = {}
         self._graph_pool = None
-        log.info("model %s on %s: %d KV pages (%.1f GB pool, %s)",
-                 cfg.model.name, self.device, self.cache.num_pages,
+        log.info("model %s (%s weights) on %s: %d KV pages (%.1f GB pool, %s)",
+                 cfg.model.name, cfg.weight_dtype, self.device,
+                 self.cache.num_pages,
                  self.cache.kv.numel() * self.cache.kv.element_size() / 1e9,
                  cfg.kv_cache_dtype)
 

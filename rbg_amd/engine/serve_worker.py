@@ -60,6 +60,7 @@ def _engine_cfg(ctx: WorkerContext) -> EngineConfig:
         kv_k_scale_log2=int(args.get("kv_k_scale_log2", 0)),
         kv_v_scale_log2=int(args.get("kv_v_scale_log2", 0)),
         prefill_kv_read=str(args.get("prefill_kv_read", "gather")),
+        weight_dtype=str(args.get("weight_dtype", "bf16")),
     )
 
 
@@ -402,6 +403,7 @@ class ServeWorker:
             out["kv_cache"] = dict(
                 self.engine.runner.cache.signature(),
                 num_pages=self.engine.runner.cache.num_pages)
+            out["weight_dtype"] = self.cfg.weight_dtype
             if self._xfer_stats["pushes"]:
                 xs = dict(self._xfer_stats)
                 xs["gb_per_s"] = round(

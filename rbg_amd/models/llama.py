@@ -50,17 +50,77 @@ class ForwardBatch:
     decode_num_splits: int = 0      # 0 = pick host-side (sync-free in graphs)
 
 
+def _weight_shard(out_f: int, in_f: int, device, dtype, gen,
+                  shard_dim: int = -1, tp_size: int = 1, tp_rank: int = 0,
+                  fp8: bool = False):
+    """Generate the FULL weight deterministically, then slice this rank's
+    shard — the model is bit-identical across TP degrees (modulo all-reduce
+    summation order), so TP=N serving is directly comparable to TP=1.
+
+    Returns (w, e).  fp8: the full weight is quantised first (e4m3 bytes and
+    one int8 exponent per output row, docs/FEATURES.md "FP8 weights"), so
+    every TP degree holds slices of ONE quantised model: a row shard takes
+    its rows' exponents, a column shard keeps them all.  Otherwise e is
+    None."""
+    w = torch.empty(out_f, in_f, device=device, dtype=dtype)
+    w.normal_(0.0, 0.02, generator=gen)
+    e = None
+    if fp8:
+        w, e = ops.quantize_weight_e4m3(w)
+    if tp_size > 1 and shard_dim >= 0:
+        w = w.chunk(tp_size, dim=shard_dim)[tp_rank].contiguous()
+        if fp8 and shard_dim == 0:
+            e = e.chunk(tp_size)[tp_rank].contiguous()
+    return w, e
+
+
 def _linear_weight(out_f: int, in_f: int, device, dtype, gen,
                    shard_dim: int = -1, tp_size: int = 1,
                    tp_rank: int = 0) -> nn.Parameter:
-    """Generate the FULL weight deterministically, then slice this rank's
-    shard — the model is bit-identical across TP degrees (modulo all-reduce
-    summation order), so TP=N serving is directly comparable to TP=1."""
-    w = torch.empty(out_f, in_f, device=device, dtype=dtype)
-    w.normal_(0.0, 0.02, generator=gen)
-    if tp_size > 1 and shard_dim >= 0:
-        w = w.chunk(tp_size, dim=shard_dim)[tp_rank].contiguous()
-    return nn.Parameter(w, requires_grad=False)
+    return nn.Parameter(_weight_shard(out_f, in_f, device, dtype, gen,
+                                      shard_dim, tp_size, tp_rank)[0],
+                        requires_grad=False)
+
+
+class W8Parameter(nn.Parameter):
+    """An e4m3 projection weight [N, K]; `scale` is the int8 [N] parameter of
+    its per-row exponents, registered beside it by its module."""
+
+    def __new__(cls, w8: torch.Tensor, scale: nn.Parameter):
+        p = super().__new__(cls, w8, False)
+        p.scale = scale
+        return p
+
+    def dequantize(self) -> torch.Tensor:
+        """The bf16 weight this one stands for: e4m3 * 2^e, exact."""
+        return ops.dequantize_weight(self.data, self.scale.data)
+
+
+def _projection(*shards):
+    """(weight, scale) parameters of a projection from the _weight_shard
+    results of its row blocks; scale is None for bf16."""
+    ws, es = zip(*shards)
+    if es[0] is None:
+        w = ws[0] if len(ws) == 1 else torch.cat(ws, dim=0)
+        return nn.Parameter(w, requires_grad=False), None
+    # cat moves bytes: it has no float8 kernel
+    w8 = torch.cat([w.view(torch.uint8) for w in ws], dim=0).view(ops.FP8)
+    if w8.shape[0] % 64:
+        raise ValueError("fp8 weights need N %% 64 == 0 per projection "
+                         "shard, got N = %d" % w8.shape[0])
+    scale = nn.Parameter(torch.cat(es), requires_grad=False)
+    return W8Parameter(w8, scale), scale
+
+
+def _linear(x: torch.Tensor, w: nn.Parameter, scale) -> torch.Tensor:
+    # a bf16 weight makes the call it always made
+    return ops.linear(x, w) if scale is None else ops.linear(x, w, scale)
+
+
+def _linear_add_rmsnorm(x, w, scale, residual, norm_weight, eps):
+    if scale is None:
+        return ops.linear_add_rmsnorm(x, w, residual, norm_weight, eps)
+    return ops.linear_add_rmsnorm(x, w, residual, norm_weight, eps, scale)
 
 
 class TPContext:
@@ -152,7 +212,7 @@ class PPContext:
 
 class LlamaAttention(nn.Module):
     def __init__(self, cfg: ModelConfig, layer_idx: int, tp: TPContext,
-                 device, dtype, gen):
+                 device, dtype, gen, fp8_weights: bool = False):
         super().__init__()
         self.cfg = cfg
         self.layer_idx = layer_idx
@@ -170,17 +230,17 @@ class LlamaAttention(nn.Module):
         # the same model (see _linear_weight).
         full_q = cfg.num_heads * cfg.head_dim
         full_kv = cfg.num_kv_heads * cfg.head_dim
-        wq = _linear_weight(full_q, cfg.hidden_size, device, dtype, gen,
-                            shard_dim=0, tp_size=tp.size, tp_rank=tp.rank)
-        wk = _linear_weight(full_kv, cfg.hidden_size, device, dtype, gen,
-                            shard_dim=0, tp_size=tp.size, tp_rank=tp.rank)
-        wv = _linear_weight(full_kv, cfg.hidden_size, device, dtype, gen,
-                            shard_dim=0, tp_size=tp.size, tp_rank=tp.rank)
-        self.wqkv = nn.Parameter(torch.cat([wq, wk, wv], dim=0),
-                                 requires_grad=False)
-        self.wo = _linear_weight(cfg.hidden_size, full_q, device, dtype, gen,
-                                 shard_dim=1, tp_size=tp.size,
-                                 tp_rank=tp.rank)
+        shard = dict(tp_size=tp.size, tp_rank=tp.rank, fp8=fp8_weights)
+        wq = _weight_shard(full_q, cfg.hidden_size, device, dtype, gen,
+                           shard_dim=0, **shard)
+        wk = _weight_shard(full_kv, cfg.hidden_size, device, dtype, gen,
+                           shard_dim=0, **shard)
+        wv = _weight_shard(full_kv, cfg.hidden_size, device, dtype, gen,
+                           shard_dim=0, **shard)
+        self.wqkv, self.wqkv_scale = _projection(wq, wk, wv)
+        self.wo, self.wo_scale = _projection(
+            _weight_shard(cfg.hidden_size, full_q, device, dtype, gen,
+                          shard_dim=1, **shard))
         self.q_out, self.kv_out = q_out, kv_out
         self.q_norm = self.k_norm = None
         if cfg.qk_norm:
@@ -199,7 +259,7 @@ class LlamaAttention(nn.Module):
         the following RMSNorm into o_proj (TP = 1 only: no all-reduce sits
         between them); the return value is then the normed hidden state."""
         T = x.shape[0]
-        qkv = ops.linear(x, self.wqkv)
+        qkv = _linear(x, self.wqkv, self.wqkv_scale)
         # q/k/v stay SLICES of the fused projection: the rope and attention
         # kernels take a token-row stride, so no .contiguous() copies
         # (~73 ms/bench of pure copy kernels before this)
@@ -278,46 +338,47 @@ class LlamaAttention(nn.Module):
                                      num_splits=batch.decode_num_splits)
         o = o.view(T, self.q_out).contiguous()
         if add_norm is not None:
-            return ops.linear_add_rmsnorm(o, self.wo, *add_norm)
-        return self.tp.all_reduce(ops.linear(o, self.wo))
+            return _linear_add_rmsnorm(o, self.wo, self.wo_scale, *add_norm)
+        return self.tp.all_reduce(_linear(o, self.wo, self.wo_scale))
 
 
 class LlamaMLP(nn.Module):
-    def __init__(self, cfg: ModelConfig, tp: TPContext, device, dtype, gen):
+    def __init__(self, cfg: ModelConfig, tp: TPContext, device, dtype, gen,
+                 fp8_weights: bool = False):
         super().__init__()
         self.tp = tp
         assert cfg.intermediate_size % tp.size == 0
         inter = cfg.intermediate_size // tp.size
-        wg = _linear_weight(cfg.intermediate_size, cfg.hidden_size, device,
-                            dtype, gen, shard_dim=0, tp_size=tp.size,
-                            tp_rank=tp.rank)
-        wu = _linear_weight(cfg.intermediate_size, cfg.hidden_size, device,
-                            dtype, gen, shard_dim=0, tp_size=tp.size,
-                            tp_rank=tp.rank)
-        self.w_gate_up = nn.Parameter(torch.cat([wg, wu], dim=0),
-                                      requires_grad=False)
-        self.w_down = _linear_weight(cfg.hidden_size, cfg.intermediate_size,
-                                     device, dtype, gen, shard_dim=1,
-                                     tp_size=tp.size, tp_rank=tp.rank)
+        shard = dict(tp_size=tp.size, tp_rank=tp.rank, fp8=fp8_weights)
+        wg = _weight_shard(cfg.intermediate_size, cfg.hidden_size, device,
+                           dtype, gen, shard_dim=0, **shard)
+        wu = _weight_shard(cfg.intermediate_size, cfg.hidden_size, device,
+                           dtype, gen, shard_dim=0, **shard)
+        self.w_gate_up, self.w_gate_up_scale = _projection(wg, wu)
+        self.w_down, self.w_down_scale = _projection(
+            _weight_shard(cfg.hidden_size, cfg.intermediate_size, device,
+                          dtype, gen, shard_dim=1, **shard))
         self.inter = inter
 
     def forward(self, x: torch.Tensor, add_norm=None) -> torch.Tensor:
         """add_norm: as in LlamaAttention.forward, fused into down_proj."""
-        gu = ops.linear(x, self.w_gate_up)
+        gu = _linear(x, self.w_gate_up, self.w_gate_up_scale)
         h = ops.silu_mul(gu)
         if add_norm is not None:
-            return ops.linear_add_rmsnorm(h, self.w_down, *add_norm)
-        return self.tp.all_reduce(ops.linear(h, self.w_down))
+            return _linear_add_rmsnorm(h, self.w_down, self.w_down_scale,
+                                       *add_norm)
+        return self.tp.all_reduce(_linear(h, self.w_down, self.w_down_scale))
 
 
 class LlamaLayer(nn.Module):
     def __init__(self, cfg: ModelConfig, layer_idx: int, tp: TPContext,
-                 device, dtype, gen):
+                 device, dtype, gen, fp8_weights: bool = False):
         super().__init__()
         # layer_idx here is the KV-cache index LOCAL to this PP stage; the
         # weight generator is already seeded by the GLOBAL layer index
-        self.attn = LlamaAttention(cfg, layer_idx, tp, device, dtype, gen)
-        self.mlp = LlamaMLP(cfg, tp, device, dtype, gen)
+        self.attn = LlamaAttention(cfg, layer_idx, tp, device, dtype, gen,
+                                   fp8_weights)
+        self.mlp = LlamaMLP(cfg, tp, device, dtype, gen, fp8_weights)
         self.input_norm = nn.Parameter(
             torch.ones(cfg.hidden_size, device=device, dtype=dtype),
             requires_grad=False)
@@ -365,8 +426,14 @@ class LlamaLayer(nn.Module):
 class LlamaForCausalLM(nn.Module):
     def __init__(self, cfg: ModelConfig, device: torch.device,
                  tp: Optional[TPContext] = None, base_seed: int = 1234,
-                 pp: Optional[PPContext] = None):
+                 pp: Optional[PPContext] = None, weight_dtype: str = "bf16"):
         super().__init__()
+        if weight_dtype not in ops.WEIGHT_DTYPES:
+            raise ValueError("unknown weight_dtype %r (one of %s)" % (
+                weight_dtype, ", ".join(ops.WEIGHT_DTYPES)))
+        # "fp8_e4m3": the four projections of every layer are e4m3 with
+        # per-row exponents; embed, the norms and lm_head stay bf16
+        self.weight_dtype = weight_dtype
         self.cfg = cfg
         self.tp = tp or TPContext()
         self.pp = pp or PPContext()
@@ -397,7 +464,7 @@ class LlamaForCausalLM(nn.Module):
                 requires_grad=False)
         self.layers = nn.ModuleList([
             LlamaLayer(cfg, i - self.layer_start, self.tp, device, dtype,
-                       _gen(1 + i))
+                       _gen(1 + i), weight_dtype == "fp8_e4m3")
             for i in range(self.layer_start, self.layer_end)])
         self.link_norm_fusion(self.tp.size == 1)
         self.final_norm = None
@@ -411,6 +478,11 @@ class LlamaForCausalLM(nn.Module):
         self.cos_sin = ops.build_cos_sin_table(
             cfg.head_dim, cfg.max_position, cfg.rope_theta,
             device=device)
+        if weight_dtype != "bf16" and device.type == "cuda":
+            # the bf16 and fp32 temporaries of quantisation are several times
+            # the bytes that stay: hand them back before the KV pool is sized
+            # from the free memory
+            torch.cuda.empty_cache()
 
     def link_norm_fusion(self, on: bool) -> None:
         """Fuse each row-parallel projection with the add + RMSNorm behind
@@ -465,7 +537,8 @@ class LlamaForCausalLM(nn.Module):
         across ranks, then copies into the live parameters (the KV pool and
         any captured hipGraphs keep their addresses)."""
         fresh = LlamaForCausalLM(self.cfg, self.device, self.tp,
-                                 base_seed=seed, pp=self.pp)
+                                 base_seed=seed, pp=self.pp,
+                                 weight_dtype=self.weight_dtype)
         with torch.no_grad():
             for p, q in zip(self.parameters(), fresh.parameters()):
                 p.copy_(q)

@@ -71,11 +71,56 @@ def _on_gpu(t: torch.Tensor) -> bool:
 SKINNY_GEMM = int(os.environ.get("RBG_SKINNY_GEMM", "1"))
 
 
-def linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+FP8 = torch.float8_e4m3fn
+WEIGHT_DTYPES = reference.WEIGHT_DTYPES
+quantize_weight_e4m3 = reference.quantize_weight_e4m3
+dequantize_weight_e4m3 = reference.dequantize_weight_e4m3
+
+
+def _is_w8(w: torch.Tensor, w_scale_log2) -> bool:
+    """True for an e4m3 weight with its exponents (docs/FEATURES.md "FP8
+    weights"); half a pair raises before anything is launched."""
+    if w.dtype == FP8:
+        if w_scale_log2 is None:
+            raise ValueError("an e4m3 weight needs w_scale_log2, its int8 "
+                             "per-row exponents")
+        return True
+    if w_scale_log2 is not None:
+        raise ValueError("w_scale_log2 was given for a %s weight: only an "
+                         "e4m3 weight has exponents" % w.dtype)
+    return False
+
+
+def _use_skinny_gemm_w8(x: torch.Tensor, w: torch.Tensor) -> bool:
+    # every N: an e4m3 weight has no library to prefer on the wide shapes
+    return bool(x.dim() == 2 and x.dtype == torch.bfloat16 and
+                1 <= x.shape[0] <= 128 and w.shape[0] % 64 == 0 and
+                x.shape[1] >= 256 and x.shape[1] % 256 == 0)
+
+
+def dequantize_weight(w: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
+    """bf16 [N, K] = e4m3 * 2^e[row], exact (hip/skinny_gemm_w8.hip's
+    w8_dequant_kernel on a GPU)."""
+    if _on_gpu(w):
+        return _require_hip().w8_dequant(w, e)
+    return reference.dequantize_weight_e4m3(w, e)
+
+
+def linear(x: torch.Tensor, w: torch.Tensor,
+           w_scale_log2=None) -> torch.Tensor:
     """Projection GEMM with decode-shape dispatch: for M <= 128 rows the
     hand-written split-K streaming kernel (hip/skinny_gemm.hip) replaces
     hipBLASLt, which leaves 2-5x on narrow-N skinny shapes
-    (profiles/gemm_ab_b128.json).  Prefill-sized M goes to the library."""
+    (profiles/gemm_ab_b128.json).  Prefill-sized M goes to the library.
+
+    An e4m3 `w` with its int8 exponents `w_scale_log2` is the bf16 weight
+    dq = e4m3 * 2^e: M <= 128 takes hip/skinny_gemm_w8.hip at every N,
+    anything else is dequantised (exactly) and goes to the library."""
+    if _is_w8(w, w_scale_log2):
+        if _on_gpu(x) and _use_skinny_gemm_w8(x, w):
+            return _require_hip().skinny_gemm_w8(
+                x if x.is_contiguous() else x.contiguous(), w, w_scale_log2)
+        return torch.nn.functional.linear(x, dequantize_weight(w, w_scale_log2))
     # measured policy (profiles/sg_micro7_b*.json): the custom kernel wins
     # on narrow-N shapes (o/down, N<=4096) at any decode batch, on mid-N
     # (qkv, 6144) only up to M=64, and never on wide-N (gate_up 28672,
@@ -96,12 +141,20 @@ def _use_skinny_gemm(x: torch.Tensor, w: torch.Tensor) -> bool:
 
 def linear_add_rmsnorm(x: torch.Tensor, w: torch.Tensor,
                        residual: torch.Tensor, norm_weight: torch.Tensor,
-                       eps: float) -> torch.Tensor:
+                       eps: float, w_scale_log2=None) -> torch.Tensor:
     """h = linear(x, w); residual += h; return rmsnorm(residual) — bit for
     bit `h = linear(x, w); fused_add_rmsnorm(h, residual, ...)`.  Where
     linear() would take the custom GEMM, the split-K partials are folded
     inside the norm kernel instead of by a reduce launch of their own
-    (hip/rmsnorm.hip, NORM_FOLD_ADD)."""
+    (hip/rmsnorm.hip, NORM_FOLD_ADD).  w_scale_log2: as in linear()."""
+    if _is_w8(w, w_scale_log2):
+        if _on_gpu(x) and _use_skinny_gemm_w8(x, w):
+            return _require_hip().skinny_gemm_w8_add_rmsnorm(
+                x if x.is_contiguous() else x.contiguous(), w, w_scale_log2,
+                residual, norm_weight, eps)
+        h = linear(x, w, w_scale_log2)
+        fused_add_rmsnorm(h, residual, norm_weight, eps)
+        return h
     if _use_skinny_gemm(x, w):
         return _require_hip().skinny_gemm_add_rmsnorm(
             x if x.is_contiguous() else x.contiguous(), w, residual,
@@ -131,7 +184,6 @@ def silu_mul(x: torch.Tensor) -> torch.Tensor:
     return reference.silu_mul(x)
 
 
-FP8 = torch.float8_e4m3fn
 KV_CACHE_DTYPES = reference.KV_CACHE_DTYPES
 KV_SCALE_LOG2_RANGE = reference.KV_SCALE_LOG2_RANGE
 check_kv_scale_log2 = reference.check_kv_scale_log2

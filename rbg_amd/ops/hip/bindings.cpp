@@ -602,29 +602,22 @@ int skinny_gemm_launch(const torch::Tensor& a, const torch::Tensor& w,
   return splits;
 }
 
-}  // namespace
-
-torch::Tensor skinny_gemm(torch::Tensor a, torch::Tensor w,
-                          int64_t force_splits = 0, int64_t panel = 0) {
-  torch::Tensor c, ws;
-  const int splits = skinny_gemm_launch(a, w, force_splits, panel, c, ws);
+// What both GEMMs leave to be done: fold the f32 partials of splits > 1.
+torch::Tensor fold_gemm_splits(const torch::Tensor& a, int64_t N, int splits,
+                               torch::Tensor c, const torch::Tensor& ws) {
   if (splits > 1) {
-    c = torch::empty({a.size(0), w.size(0)}, a.options());
+    c = torch::empty({a.size(0), N}, a.options());
     LAUNCH(launch_reduce_splits, c.data_ptr(), ws.data_ptr(), splits,
            (long)c.numel(), current_stream());
   }
   return c;
 }
 
-// h = rmsnorm(a w^T + residual) * norm_weight with residual := a w^T +
-// residual in place: bit for bit skinny_gemm followed by fused_add_rmsnorm,
-// but the split-K fold happens in the norm kernel's prologue instead of a
-// reduce_splits launch (and a bf16 round trip) of its own.
-torch::Tensor skinny_gemm_add_rmsnorm(torch::Tensor a, torch::Tensor w,
-                                      torch::Tensor residual,
-                                      torch::Tensor norm_weight, double eps,
-                                      int64_t force_splits = 0,
-                                      int64_t panel = 0) {
+// The add + RMSNorm arguments of both fused GEMMs, checked before the GEMM
+// allocates or launches anything.
+void check_add_rmsnorm_args(const torch::Tensor& a, const torch::Tensor& w,
+                            const torch::Tensor& residual,
+                            const torch::Tensor& norm_weight) {
   check_bf16_contig(residual, "residual");
   check_bf16_contig(norm_weight, "norm_weight");
   TORCH_CHECK(a.dim() == 2 && w.dim() == 2, "a and w must be 2-D");
@@ -636,19 +629,135 @@ torch::Tensor skinny_gemm_add_rmsnorm(torch::Tensor a, torch::Tensor w,
   TORCH_CHECK(residual.device() == a.device() &&
                   norm_weight.device() == a.device(),
               "a/residual/norm_weight device mismatch");
-  torch::Tensor c, ws;
-  const int splits = skinny_gemm_launch(a, w, force_splits, panel, c, ws);
-  const int M = (int)a.size(0), N = (int)w.size(0);
+}
+
+// residual += gemm; return rmsnorm(residual) * norm_weight, from the bf16
+// result `c` (splits == 1) or the partials `ws`, which the norm kernel folds
+// in its prologue instead of a reduce_splits launch (and a bf16 round trip)
+// of its own.
+torch::Tensor add_rmsnorm_after_gemm(const torch::Tensor& a, int64_t N,
+                                     int splits, torch::Tensor c,
+                                     const torch::Tensor& ws,
+                                     torch::Tensor& residual,
+                                     const torch::Tensor& norm_weight,
+                                     double eps) {
+  const int M = (int)a.size(0);
   if (splits == 1) {
     LAUNCH(launch_fused_add_rmsnorm, c.data_ptr(), residual.data_ptr(),
-           norm_weight.data_ptr(), (float)eps, M, N, current_stream());
+           norm_weight.data_ptr(), (float)eps, M, (int)N, current_stream());
     return c;
   }
-  c = torch::empty({a.size(0), w.size(0)}, a.options());
+  c = torch::empty({a.size(0), N}, a.options());
   LAUNCH(launch_fold_add_rmsnorm, c.data_ptr(), ws.data_ptr(),
          residual.data_ptr(), norm_weight.data_ptr(), (float)eps, splits, M,
-         N, current_stream());
+         (int)N, current_stream());
   return c;
+}
+
+// ---- FP8 weights (skinny_gemm_w8.hip; docs/FEATURES.md "FP8 weights") ------
+
+// w8 e4m3 [N, K] and its exponents e int8 [N], on `device`.
+void check_w8_pair(const torch::Tensor& w8, const torch::Tensor& e,
+                   const torch::Device& device) {
+  TORCH_CHECK(w8.is_cuda(), "w8 must be on GPU");
+  TORCH_CHECK(w8.scalar_type() == torch::kFloat8_e4m3fn,
+              "w8 must be float8_e4m3fn");
+  TORCH_CHECK(w8.is_contiguous() && w8.dim() == 2,
+              "w8 must be contiguous and 2-D");
+  TORCH_CHECK(e.scalar_type() == torch::kChar, "e must be int8");
+  TORCH_CHECK(e.is_contiguous() && e.numel() == w8.size(0),
+              "e must be contiguous with one exponent per row of w8");
+  TORCH_CHECK(w8.device() == device && e.device() == device,
+              "a, w8 and e must be on one device");
+}
+
+// skinny_gemm_launch for an e4m3 weight: every check, then the GEMM.
+int skinny_gemm_w8_launch(const torch::Tensor& a, const torch::Tensor& w8,
+                          const torch::Tensor& e, int64_t force_splits,
+                          torch::Tensor& c, torch::Tensor& ws) {
+  check_bf16_contig(a, "a");
+  TORCH_CHECK(a.dim() == 2, "a must be 2-D");
+  check_w8_pair(w8, e, a.device());
+  const int64_t M = a.size(0), K = a.size(1), N = w8.size(0);
+  TORCH_CHECK(w8.size(1) == K, "K mismatch");
+  TORCH_CHECK(M >= 1 && M <= 128, "M must be in [1, 128], got ", M);
+  TORCH_CHECK(N >= 64 && N % 64 == 0, "N must be a multiple of 64, got ", N);
+  TORCH_CHECK(force_splits == 0 || force_splits == 1 || force_splits == 2 ||
+                  force_splits == 4 || force_splits == 8,
+              "force_splits must be 0 (auto), 1, 2, 4 or 8");
+  // the bf16 GEMM's policy, so that both engines split alike
+  const int splits = force_splits > 0 ? (int)force_splits
+                                      : pick_gemm_splits((int)N, (int)K);
+  TORCH_CHECK(K >= 256 && K % (splits * 256) == 0,
+              "K must be a multiple of splits * 256");
+  void* cp = nullptr;
+  void* wsp = nullptr;
+  if (splits > 1) {
+    ws = torch::empty({splits, M, N}, a.options().dtype(torch::kFloat32));
+    wsp = ws.data_ptr();
+  } else {
+    c = torch::empty({M, N}, a.options());
+    cp = c.data_ptr();
+  }
+  LAUNCH(launch_skinny_gemm_w8, cp, wsp, a.data_ptr(), w8.data_ptr(),
+         e.data_ptr(), (int)M, (int)N, (int)K, splits, current_stream());
+  return splits;
+}
+
+}  // namespace
+
+torch::Tensor skinny_gemm(torch::Tensor a, torch::Tensor w,
+                          int64_t force_splits = 0, int64_t panel = 0) {
+  torch::Tensor c, ws;
+  const int splits = skinny_gemm_launch(a, w, force_splits, panel, c, ws);
+  return fold_gemm_splits(a, w.size(0), splits, c, ws);
+}
+
+// h = rmsnorm(a w^T + residual) * norm_weight with residual := a w^T +
+// residual in place: bit for bit skinny_gemm followed by fused_add_rmsnorm.
+torch::Tensor skinny_gemm_add_rmsnorm(torch::Tensor a, torch::Tensor w,
+                                      torch::Tensor residual,
+                                      torch::Tensor norm_weight, double eps,
+                                      int64_t force_splits = 0,
+                                      int64_t panel = 0) {
+  check_add_rmsnorm_args(a, w, residual, norm_weight);
+  torch::Tensor c, ws;
+  const int splits = skinny_gemm_launch(a, w, force_splits, panel, c, ws);
+  return add_rmsnorm_after_gemm(a, w.size(0), splits, c, ws, residual,
+                                norm_weight, eps);
+}
+
+// C = a dq(w8)^T, bit for bit skinny_gemm(a, dq(w8), force_splits).
+torch::Tensor skinny_gemm_w8(torch::Tensor a, torch::Tensor w8,
+                             torch::Tensor e, int64_t force_splits = 0) {
+  torch::Tensor c, ws;
+  const int splits = skinny_gemm_w8_launch(a, w8, e, force_splits, c, ws);
+  return fold_gemm_splits(a, w8.size(0), splits, c, ws);
+}
+
+torch::Tensor skinny_gemm_w8_add_rmsnorm(torch::Tensor a, torch::Tensor w8,
+                                         torch::Tensor e,
+                                         torch::Tensor residual,
+                                         torch::Tensor norm_weight, double eps,
+                                         int64_t force_splits = 0) {
+  check_add_rmsnorm_args(a, w8, residual, norm_weight);
+  torch::Tensor c, ws;
+  const int splits = skinny_gemm_w8_launch(a, w8, e, force_splits, c, ws);
+  return add_rmsnorm_after_gemm(a, w8.size(0), splits, c, ws, residual,
+                                norm_weight, eps);
+}
+
+// bf16 [N, K] = e4m3(w8) * 2^e[row] (exact), for the shapes the GEMM above
+// does not serve.
+torch::Tensor w8_dequant(torch::Tensor w8, torch::Tensor e) {
+  check_w8_pair(w8, e, w8.device());
+  const int64_t N = w8.size(0), K = w8.size(1);
+  TORCH_CHECK(K % 16 == 0, "K must be a multiple of 16, got ", K);
+  auto out = torch::empty({N, K}, w8.options().dtype(torch::kBFloat16));
+  if (out.numel() == 0) return out;
+  LAUNCH(launch_w8_dequant, out.data_ptr(), w8.data_ptr(), e.data_ptr(),
+         (long)N, (long)K, current_stream());
+  return out;
 }
 
 
@@ -894,6 +1003,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("a"), py::arg("w"), py::arg("residual"),
         py::arg("norm_weight"), py::arg("eps"), py::arg("force_splits") = 0,
         py::arg("panel") = 0);
+  m.def("skinny_gemm_w8", &skinny_gemm_w8,
+        "decode-shape GEMM over e4m3 weights with per-row 2^e scales",
+        py::arg("a"), py::arg("w8"), py::arg("e"),
+        py::arg("force_splits") = 0);
+  m.def("skinny_gemm_w8_add_rmsnorm", &skinny_gemm_w8_add_rmsnorm,
+        "skinny_gemm_w8 + fused_add_rmsnorm with the split-K fold inside the "
+        "norm kernel; returns h, updates residual in place",
+        py::arg("a"), py::arg("w8"), py::arg("e"), py::arg("residual"),
+        py::arg("norm_weight"), py::arg("eps"), py::arg("force_splits") = 0);
+  m.def("w8_dequant", &w8_dequant,
+        "e4m3 [N, K] + int8 exponents [N] -> bf16 [N, K]");
   m.def("sample", &sample,
         "seeded top-k/min-p/top-p Gumbel-max sampler -> (tokens, num_kept)");
   // gil_scoped_release on the IPC/copy entry points: mapping or launching

@@ -154,6 +154,16 @@ hipError_t launch_skinny_gemm_wide(void* c, void* ws, const void* a,
 hipError_t launch_reduce_splits(void* c, const void* ws, int splits, long mn,
                                 hipStream_t stream);
 
+// FP8 weights (skinny_gemm_w8.hip): w8 e4m3 [N, K] with one power-of-two
+// exponent per row, e int8 [N].  The GEMM has 1 <= M <= 128, N % 64 == 0,
+// K % (splits * 256) == 0 and writes c / ws as launch_skinny_gemm does, the
+// rows already scaled; the dequant writes bf16 [N, K], K % 16 == 0.
+hipError_t launch_skinny_gemm_w8(void* c, void* ws, const void* a,
+                                 const void* w8, const void* e, int M, int N,
+                                 int K, int splits, hipStream_t stream);
+hipError_t launch_w8_dequant(void* out, const void* w8, const void* e, long N,
+                             long K, hipStream_t stream);
+
 hipError_t launch_sample(void* out_tok, void* out_kept, const void* logits,
                          const void* temperature, const void* top_k,
                          const void* top_p, const void* min_p,

@@ -90,6 +90,50 @@ def dequantize_e4m3(b: torch.Tensor, scale_log2: int = 0,
     return (b.float() * (2.0 ** scale_log2)).to(dtype)
 
 
+# FP8 (e4m3) projection weights (docs/FEATURES.md "FP8 weights"): bytes
+# [N, K] with one power-of-two exponent per output row, int8 [N].
+WEIGHT_DTYPES = ("bf16", "fp8_e4m3")
+W_SCALE_LOG2_RANGE = (-64, 64)
+
+
+def weight_scale_log2(w: torch.Tensor) -> torch.Tensor:
+    """int8 [N]: per row the smallest e with amax <= 448 * 2^e, clamped to
+    W_SCALE_LOG2_RANGE, 0 for an all-zero row.  From the exponent and
+    mantissa of amax, not from a division that could round: amax = m * 2^x
+    with m in [0.5, 1) and 448 = 0.875 * 2^9, so e = x - 9 where m <= 0.875
+    and x - 8 above."""
+    amax = w.float().abs().amax(dim=1)
+    m, x = torch.frexp(amax)
+    e = torch.where(m <= 0.875, x - 9, x - 8)
+    e = torch.where(amax > 0, e, torch.zeros_like(e))
+    return e.clamp(*W_SCALE_LOG2_RANGE).to(torch.int8)
+
+
+def quantize_weight_e4m3(w: torch.Tensor
+                         ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """W [N, K] -> (w8 e4m3 [N, K], e int8 [N]): row n is quantize_e4m3 of
+    W[n] * 2^-e[n] (the scaling is exact, so the one rounding is e4m3's)."""
+    if w.dim() != 2:
+        raise ValueError("a projection weight is 2-D, got %s" % (
+            tuple(w.shape),))
+    e = weight_scale_log2(w)
+    scaled = torch.ldexp(w.float(), -e.to(torch.int32).unsqueeze(1))
+    return quantize_e4m3(scaled), e
+
+
+def dequantize_weight_e4m3(w8: torch.Tensor, e: torch.Tensor
+                           ) -> torch.Tensor:
+    """dq[n, k] = e4m3(w8[n, k]) * 2^e[n] as bf16: exact, and a normal bf16
+    or zero for every |e| <= 64."""
+    if w8.dtype != torch.float8_e4m3fn or e.dtype != torch.int8 or \
+            w8.dim() != 2 or e.numel() != w8.shape[0]:
+        raise ValueError("need e4m3 [N, K] and int8 [N], got %s %s and %s %s"
+                         % (w8.dtype, tuple(w8.shape), e.dtype,
+                            tuple(e.shape)))
+    return torch.ldexp(w8.float(),
+                       e.to(torch.int32).view(-1, 1)).to(torch.bfloat16)
+
+
 def kv_gather_dequant(cache: torch.Tensor, slots: torch.Tensor,
                       scale_log2: int = 0) -> torch.Tensor:
     page_size = cache.shape[2]

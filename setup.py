@@ -29,6 +29,7 @@ HIP_SOURCES = [
     "kv_fp8.hip",
     "silu_mul.hip",
     "skinny_gemm.hip",
+    "skinny_gemm_w8.hip",
     "sampling.hip",
     "kv_peer_copy.hip",
     "allreduce.hip",

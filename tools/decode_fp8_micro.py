@@ -139,8 +139,10 @@ def engine_rows(args):
     from rbg_amd.engine.sequence import SamplingParams
     B, ctx, new = 128, 2048, 4 + args.engine_rounds * args.engine_steps + 8
     engines = {}
-    for name in ("bf16", "fp8"):
-        kw = {} if name == "bf16" else dict(kv_cache_dtype="fp8_e4m3")
+    variants = {"bf16": {}, "fp8": dict(kv_cache_dtype="fp8_e4m3")}
+    if args.engine_weights:       # FP8 projection weights over a bf16 pool
+        variants = {"bf16": {}, "fp8w": dict(weight_dtype="fp8_e4m3")}
+    for name, kw in variants.items():
         cfg = EngineConfig(model=ModelConfig.preset("llama-3-8b"),
                            device="cuda", max_batch_size=B,
                            max_seq_len=ctx + new + 16,
@@ -187,11 +189,14 @@ def main() -> None:
     ap.add_argument("--engine-rounds", type=int, default=5)
     ap.add_argument("--engine-steps", type=int, default=20)
     ap.add_argument("--no-engine", action="store_true")
+    ap.add_argument("--engine-weights", action="store_true",
+                    help="engine rows only: bf16 against fp8_e4m3 weights")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     assert ops.HAVE_HIP, ops._hip_err
-    results = decode_rows(args) + store_rows(args)
+    results = [] if args.engine_weights else (decode_rows(args) +
+                                              store_rows(args))
     if not args.no_engine:
         results += engine_rows(args)
     if args.out:

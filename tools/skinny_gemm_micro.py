@@ -9,6 +9,11 @@ so each weight streams from HBM as it does in a real decode step (16 GB of
 weights per step).  `--warm` keeps the older behaviour, one weight tensor
 timed over and over (a 33 MB weight then sits in the Infinity Cache), so that
 profiles/sg_micro7_b*.json stay comparable.
+
+`--w8` times FP8 weights instead: what ops.linear does for a bf16 weight at
+that shape today (custom kernel or library) alternated with skinny_gemm_w8 on
+the quantised copy of the same weights, in us and in TB/s of WEIGHT bytes
+(profiles/gemm_w8_micro.json).
 """
 import argparse
 import json
@@ -50,6 +55,8 @@ def main():
                          "(0 = the launcher's choice)")
     ap.add_argument("--warm", action="store_true",
                     help="one weight tensor per shape, re-read every call")
+    ap.add_argument("--w8", action="store_true",
+                    help="ops.linear on bf16 weights against skinny_gemm_w8")
     ap.add_argument("--out", default=None, help="also write the JSON here")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -68,7 +75,11 @@ def main():
                   for _ in range(n_w)]
             x = torch.randn(M, k, dtype=torch.bfloat16, device=dev)
             cands = [("lib", lambda i: torch.nn.functional.linear(x, ws[i]))]
-            for s in splits:
+            if args.w8:
+                q = [ops.quantize_weight_e4m3(w) for w in ws]
+                cands = [("bf16", lambda i: ops.linear(x, ws[i])),
+                         ("w8", lambda i: hip.skinny_gemm_w8(x, *q[i]))]
+            for s in () if args.w8 else splits:
                 if k % (max(s, 1) * 256):
                     continue
                 for panel in (32, 64):
@@ -78,7 +89,7 @@ def main():
                         "s%s_p%d" % (s or "auto", panel),
                         lambda i, s=s, panel=panel: hip.skinny_gemm(
                             x, ws[i], s, panel)))
-            if n == H:
+            if n == H and not args.w8:
                 # o / down: the projection with the add + norm behind it
                 res = torch.randn(M, n, dtype=torch.bfloat16, device=dev)
                 nw = torch.ones(n, dtype=torch.bfloat16, device=dev)
@@ -101,6 +112,10 @@ def main():
         for key, ms in sorted(best.items()):
             k, n = shapes[key.split("/")[0]]
             row[key + "_us"] = round(ms * 1e3, 2)
+            if args.w8:
+                wbytes = k * n * (1 if key.endswith("/w8") else 2)
+                row[key + "_weight_TBps"] = round(wbytes / ms / 1e9, 2)
+                continue
             row[key + "_GBps"] = round(
                 (k * n * 2 + M * (k + n) * 2) / ms / 1e6, 1)
         out["batch%d" % M] = row
