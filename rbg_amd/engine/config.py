@@ -41,6 +41,35 @@ class ModelConfig:
     max_position: int = 16384
     dtype: str = "bfloat16"
     qk_norm: bool = False      # Qwen3-style per-head RMSNorm on q/k
+    # Mixture of experts (docs/FEATURES.md): num_experts == 0 is the dense
+    # model; otherwise every layer's FFN is num_experts SwiGLU experts of
+    # moe_intermediate_size, num_experts_per_tok of them per token
+    num_experts: int = 0
+    num_experts_per_tok: int = 0
+    moe_intermediate_size: int = 0
+    norm_topk_prob: bool = True
+
+    def check_moe(self, tp_size: int = 1, weight_dtype: str = "bf16") -> None:
+        """Raises ValueError for an expert configuration the kernels do not
+        serve (hip/moe.hip)."""
+        if self.num_experts == 0:
+            return
+        E, k = self.num_experts, self.num_experts_per_tok
+        if tp_size > 1:
+            raise ValueError("experts with tp_size %d: tensor / expert "
+                             "parallelism is not implemented" % tp_size)
+        if weight_dtype != "bf16":
+            raise ValueError("experts need weight_dtype 'bf16', got %r"
+                             % weight_dtype)
+        if not 1 <= E <= 256 or not 1 <= k <= 8 or k > E:
+            raise ValueError("need 1 <= num_experts <= 256 and 1 <= "
+                             "num_experts_per_tok <= min(8, num_experts), got "
+                             "%d and %d" % (E, k))
+        if (self.moe_intermediate_size <= 0 or
+                self.moe_intermediate_size % 64 or self.hidden_size % 256):
+            raise ValueError("experts need moe_intermediate_size %% 64 == 0 "
+                             "and hidden_size %% 256 == 0, got %d and %d" % (
+                                 self.moe_intermediate_size, self.hidden_size))
 
     @property
     def q_size(self) -> int:
@@ -78,6 +107,16 @@ class ModelConfig:
                                vocab_size=151936, rope_theta=1e6,
                                rms_eps=1e-6, max_position=40960,
                                qk_norm=True)
+        if name in ("qwen3-30b-a3b", "qwen3-moe", "30b-a3b"):
+            # sparse: 128 experts of 768, 8 per token (3.3 B active of 30 B)
+            return ModelConfig(name="qwen3-30b-a3b", hidden_size=2048,
+                               intermediate_size=6144, num_layers=48,
+                               num_heads=32, num_kv_heads=4, head_dim=128,
+                               vocab_size=151936, rope_theta=1e6,
+                               rms_eps=1e-6, max_position=40960,
+                               qk_norm=True, num_experts=128,
+                               num_experts_per_tok=8,
+                               moe_intermediate_size=768)
         if name == "tiny-qwen":   # qk-norm CPU test shape
             return ModelConfig(name="tiny-qwen", hidden_size=256,
                                intermediate_size=512, num_layers=2,
@@ -140,6 +179,7 @@ class EngineConfig:
                 self.page_size != 16 or self.model.head_dim != 128):
             raise ValueError("prefill_kv_read 'paged' needs page_size 16 and "
                              "head_dim 128")
+        self.model.check_moe(self.tp_size, self.weight_dtype)
         kv_element_size(self.kv_cache_dtype)       # raises on an unknown name
         for name in ("kv_k_scale_log2", "kv_v_scale_log2"):
             e = getattr(self, name)

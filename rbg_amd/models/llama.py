@@ -370,6 +370,32 @@ class LlamaMLP(nn.Module):
         return self.tp.all_reduce(_linear(h, self.w_down, self.w_down_scale))
 
 
+class MoEBlock(nn.Module):
+    """The FFN of a mixture-of-experts layer (cfg.num_experts > 0): a bf16
+    router and num_experts SwiGLU experts, num_experts_per_tok per token
+    (docs/FEATURES.md "Mixture of experts")."""
+
+    def __init__(self, cfg: ModelConfig, device, dtype, gen):
+        super().__init__()
+        E, H, I = cfg.num_experts, cfg.hidden_size, cfg.moe_intermediate_size
+        self.top_k = cfg.num_experts_per_tok
+        self.renormalize = cfg.norm_topk_prob
+
+        def draw(*shape):
+            t = torch.empty(*shape, device=device, dtype=dtype)
+            return nn.Parameter(t.normal_(0.0, 0.02, generator=gen),
+                                requires_grad=False)
+
+        self.w_router = draw(E, H)
+        self.w1 = draw(E, 2 * I, H)      # gate rows [0, I), up rows [I, 2I)
+        self.w2 = draw(E, H, I)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        ids, w = ops.moe_route(ops.linear(x, self.w_router), self.top_k,
+                               self.renormalize)
+        return ops.moe_ffn(x, self.w1, self.w2, ids, w)
+
+
 class LlamaLayer(nn.Module):
     def __init__(self, cfg: ModelConfig, layer_idx: int, tp: TPContext,
                  device, dtype, gen, fp8_weights: bool = False):
@@ -378,7 +404,13 @@ class LlamaLayer(nn.Module):
         # weight generator is already seeded by the GLOBAL layer index
         self.attn = LlamaAttention(cfg, layer_idx, tp, device, dtype, gen,
                                    fp8_weights)
-        self.mlp = LlamaMLP(cfg, tp, device, dtype, gen, fp8_weights)
+        # a MoE block returns y and the next layer adds and norms as an
+        # unfused layer does: no down_proj for linear_add_rmsnorm to fuse into
+        self.moe = cfg.num_experts > 0
+        if self.moe:
+            self.mlp = MoEBlock(cfg, device, dtype, gen)
+        else:
+            self.mlp = LlamaMLP(cfg, tp, device, dtype, gen, fp8_weights)
         self.input_norm = nn.Parameter(
             torch.ones(cfg.hidden_size, device=device, dtype=dtype),
             requires_grad=False)
@@ -436,6 +468,7 @@ class LlamaForCausalLM(nn.Module):
         self.weight_dtype = weight_dtype
         self.cfg = cfg
         self.tp = tp or TPContext()
+        cfg.check_moe(self.tp.size, weight_dtype)
         self.pp = pp or PPContext()
         self.base_seed = base_seed
         self.device = device
@@ -489,10 +522,12 @@ class LlamaForCausalLM(nn.Module):
         it (LlamaLayer.fuse_norms); down_proj of local layer i applies layer
         i+1's input_norm, so the two layers are switched together."""
         layers = list(self.layers)
+        # (a MoE layer fuses o_proj only: its block has no down_proj GEMM)
+        fuse_down = on and self.cfg.num_experts == 0
         for i, layer in enumerate(layers):
-            nxt = layers[i + 1] if on and i + 1 < len(layers) else None
+            nxt = layers[i + 1] if fuse_down and i + 1 < len(layers) else None
             layer.fuse_norms = on
-            layer.input_prenormed = on and i > 0
+            layer.input_prenormed = fuse_down and i > 0
             layer.next_input_norm = () if nxt is None else (nxt.input_norm,)
 
     @property

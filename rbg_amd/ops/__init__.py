@@ -184,6 +184,102 @@ def silu_mul(x: torch.Tensor) -> torch.Tensor:
     return reference.silu_mul(x)
 
 
+# ---- mixture of experts (docs/FEATURES.md "Mixture of experts") -----------
+
+MOE_MAX_EXPERTS = reference.MOE_MAX_EXPERTS
+MOE_MAX_TOP_K = reference.MOE_MAX_TOP_K
+
+_moe_tickets: dict = {}
+
+
+def _moe_ticket(device) -> torch.Tensor:
+    """The int32 the route kernel's workgroups count themselves off on; the
+    last one puts it back to zero, so one per device serves every launch
+    (launches that follow each other on a stream, as the engine's do; two
+    streams routing at once would need a ticket each)."""
+    t = _moe_tickets.get(device)
+    if t is None:
+        t = _moe_tickets[device] = torch.zeros(1, dtype=torch.int32,
+                                               device=device)
+    return t
+
+
+def moe_route(router_logits: torch.Tensor, top_k: int,
+              renormalize: bool = True):
+    """Top-k routing of bf16 router logits [T, E] -> (ids int32 [T, k],
+    w fp32 [T, k]): the k largest logits (ties to the lower index, NaN as
+    -inf) in descending order and their fp32 softmax weights, renormalised
+    over the k selected if asked.  On a GPU the same launch also groups the
+    (token, slot) pairs by expert; the grouping rides on `ids` for
+    moe_ffn."""
+    if router_logits.dim() != 2 or router_logits.dtype != torch.bfloat16:
+        raise ValueError("router_logits must be bf16 [T, E]")
+    E = router_logits.shape[1]
+    if not 1 <= E <= MOE_MAX_EXPERTS:
+        raise ValueError("E must be in [1, %d], got %d" % (MOE_MAX_EXPERTS, E))
+    if not 1 <= top_k <= min(MOE_MAX_TOP_K, E):
+        raise ValueError("top_k must be in [1, min(%d, E)], got %d" % (
+            MOE_MAX_TOP_K, top_k))
+    if not _on_gpu(router_logits):
+        return reference.moe_route(router_logits, top_k, renormalize)
+    ids, w, offsets, pairs = _require_hip().moe_route(
+        router_logits if router_logits.is_contiguous()
+        else router_logits.contiguous(),
+        _moe_ticket(router_logits.device), top_k, bool(renormalize))
+    # in [0, E) by construction: moe_ffn neither groups nor checks them again
+    ids._moe_group = (E, offsets, pairs)
+    return ids, w
+
+
+def moe_ffn(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
+            ids: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """y bf16 [T, H] = sum_j w[t, j] * FFN_{ids[t, j]}(x[t]) with expert
+    weights w1 [E, 2I, H] (gate rows, then up rows) and w2 [E, H, I]:
+    hip/moe.hip on a GPU, reference.moe_ffn on CPU tensors.  Everything is
+    checked before anything is launched; ids that did not come from
+    moe_route are read back once for their range."""
+    for t, name, dt, nd in ((x, "x", torch.bfloat16, 2),
+                            (w1, "w1", torch.bfloat16, 3),
+                            (w2, "w2", torch.bfloat16, 3),
+                            (ids, "ids", torch.int32, 2),
+                            (w, "w", torch.float32, 2)):
+        if t.dtype != dt or t.dim() != nd:
+            raise ValueError("%s must be %d-D %s, got %s %s" % (
+                name, nd, dt, tuple(t.shape), t.dtype))
+        if t.device != x.device:
+            raise ValueError("%s is on %s but x is on %s" % (
+                name, t.device, x.device))
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+    T, H = x.shape
+    E, I, k = w1.shape[0], w2.shape[2], ids.shape[1]
+    if tuple(w1.shape) != (E, 2 * I, H) or tuple(w2.shape) != (E, H, I):
+        raise ValueError("w1 must be [E, 2I, H] and w2 [E, H, I], got %s and "
+                         "%s for H = %d" % (tuple(w1.shape), tuple(w2.shape),
+                                            H))
+    if tuple(ids.shape) != (T, k) or tuple(w.shape) != (T, k):
+        raise ValueError("ids and w must be [T, k], got %s and %s for T = %d"
+                         % (tuple(ids.shape), tuple(w.shape), T))
+    if (not 1 <= E <= MOE_MAX_EXPERTS or not 1 <= k <= min(MOE_MAX_TOP_K, E)
+            or H % 256 or I % 64):
+        raise ValueError("moe_ffn needs E <= %d, k <= min(%d, E), H %% 256 == "
+                         "0 and I %% 64 == 0, got E = %d, k = %d, H = %d, I = "
+                         "%d" % (MOE_MAX_EXPERTS, MOE_MAX_TOP_K, E, k, H, I))
+    if T == 0:
+        return torch.empty_like(x)
+    group = getattr(ids, "_moe_group", None)
+    if group is None or group[0] != E:
+        lo, hi = int(ids.min()), int(ids.max())
+        if lo < 0 or hi >= E:
+            raise ValueError("ids must lie in [0, %d), got [%d, %d]" % (
+                E, lo, hi))
+        if _on_gpu(x):
+            group = (E,) + tuple(_require_hip().moe_group(ids, E))
+    if not _on_gpu(x):
+        return reference.moe_ffn(x, w1, w2, ids, w)
+    return _require_hip().moe_ffn(x, w1, w2, w, group[1], group[2])
+
+
 KV_CACHE_DTYPES = reference.KV_CACHE_DTYPES
 KV_SCALE_LOG2_RANGE = reference.KV_SCALE_LOG2_RANGE
 check_kv_scale_log2 = reference.check_kv_scale_log2

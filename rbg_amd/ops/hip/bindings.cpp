@@ -761,6 +761,125 @@ torch::Tensor w8_dequant(torch::Tensor w8, torch::Tensor e) {
 }
 
 
+// ---- mixture of experts (moe.hip; docs/FEATURES.md "Mixture of experts") ---
+
+namespace {
+
+constexpr int64_t kMoeMaxExperts = 256, kMoeMaxTopK = 8;
+// T * k pair indices and their rows of H or I elements are int32 / size_t in
+// the kernels; the bound keeps T * k * 8 far inside int32 too
+constexpr int64_t kMoeMaxPairs = 1 << 24;
+
+void check_i32_on(const torch::Tensor& t, const char* name,
+                  const torch::Device& device, int64_t numel) {
+  check_i32_gpu(t, name);
+  TORCH_CHECK(t.device() == device, name, " is on another device");
+  TORCH_CHECK(t.numel() == numel, name, " must have ", numel, " elements");
+}
+
+// The expert weights of one layer, w1 [E, 2I, H] and w2 [E, H, I] on x's
+// device, for the shapes the grouped GEMMs serve.
+void check_moe_experts(const torch::Tensor& x, const torch::Tensor& w1,
+                       const torch::Tensor& w2) {
+  check_bf16_contig(x, "x");
+  check_bf16_contig(w1, "w1");
+  check_bf16_contig(w2, "w2");
+  TORCH_CHECK(x.dim() == 2, "x must be [T, H]");
+  TORCH_CHECK(w1.dim() == 3 && w2.dim() == 3,
+              "w1 must be [E, 2I, H] and w2 [E, H, I]");
+  TORCH_CHECK(w1.device() == x.device() && w2.device() == x.device(),
+              "x/w1/w2 device mismatch");
+  const int64_t H = x.size(1), E = w1.size(0), I = w2.size(2);
+  TORCH_CHECK(E >= 1 && E <= kMoeMaxExperts, "E must be in [1, 256], got ", E);
+  TORCH_CHECK(H >= 256 && H % 256 == 0, "H must be a multiple of 256, got ",
+              H);
+  TORCH_CHECK(I >= 64 && I % 64 == 0, "I must be a multiple of 64, got ", I);
+  TORCH_CHECK(w1.size(1) == 2 * I && w1.size(2) == H, "w1 must be [E, 2I, H]");
+  TORCH_CHECK(w2.size(0) == E && w2.size(1) == H, "w2 must be [E, H, I]");
+}
+
+}  // namespace
+
+// (ids int32 [T, k], weights f32 [T, k], expert_offsets int32 [E + 1],
+// sorted_pairs int32 [T * k]) of bf16 router logits [T, E]; ticket is the
+// caller's zeroed int32 [1].
+std::vector<torch::Tensor> moe_route(torch::Tensor logits, torch::Tensor ticket,
+                                     int64_t top_k, bool renormalize) {
+  check_bf16_contig(logits, "router_logits");
+  TORCH_CHECK(logits.dim() == 2, "router_logits must be [T, E]");
+  const int64_t T = logits.size(0), E = logits.size(1);
+  TORCH_CHECK(E >= 1 && E <= kMoeMaxExperts, "E must be in [1, 256], got ", E);
+  TORCH_CHECK(top_k >= 1 && top_k <= kMoeMaxTopK && top_k <= E,
+              "top_k must be in [1, min(8, E)], got ", top_k);
+  TORCH_CHECK(T * top_k <= kMoeMaxPairs, "too many (token, expert) pairs");
+  check_i32_on(ticket, "ticket", logits.device(), 1);
+  auto i32 = logits.options().dtype(torch::kInt32);
+  auto ids = torch::empty({T, top_k}, i32);
+  auto w = torch::empty({T, top_k}, logits.options().dtype(torch::kFloat32));
+  auto sorted = torch::empty({T * top_k}, i32);
+  if (T == 0) return {ids, w, torch::zeros({E + 1}, i32), sorted};
+  auto offsets = torch::empty({E + 1}, i32);
+  LAUNCH(launch_moe_route, ids.data_ptr(), w.data_ptr(), offsets.data_ptr(),
+         sorted.data_ptr(), ticket.data_ptr(), logits.data_ptr(), (int)T,
+         (int)E, (int)top_k, renormalize ? 1 : 0, current_stream());
+  return {ids, w, offsets, sorted};
+}
+
+// (expert_offsets, sorted_pairs) of ids [T, k] whose values the caller has
+// checked to lie in [0, E).
+std::vector<torch::Tensor> moe_group(torch::Tensor ids, int64_t E) {
+  check_i32_gpu(ids, "ids");
+  TORCH_CHECK(ids.dim() == 2, "ids must be [T, k]");
+  TORCH_CHECK(E >= 1 && E <= kMoeMaxExperts, "E must be in [1, 256], got ", E);
+  TORCH_CHECK(ids.numel() <= kMoeMaxPairs, "too many (token, expert) pairs");
+  auto sorted = torch::empty({ids.numel()}, ids.options());
+  if (ids.numel() == 0) return {torch::zeros({E + 1}, ids.options()), sorted};
+  auto offsets = torch::empty({E + 1}, ids.options());
+  LAUNCH(launch_moe_group, offsets.data_ptr(), sorted.data_ptr(),
+         ids.data_ptr(), (int)ids.numel(), (int)E, current_stream());
+  return {offsets, sorted};
+}
+
+// y bf16 [T, H] from the grouping of moe_route / moe_group.
+torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor w1, torch::Tensor w2,
+                      torch::Tensor weights, torch::Tensor expert_offsets,
+                      torch::Tensor sorted_pairs) {
+  check_moe_experts(x, w1, w2);
+  const int64_t T = x.size(0), H = x.size(1), E = w1.size(0), I = w2.size(2);
+  TORCH_CHECK(weights.is_cuda() && weights.device() == x.device() &&
+                  weights.scalar_type() == torch::kFloat32 &&
+                  weights.is_contiguous() && weights.dim() == 2 &&
+                  weights.size(0) == T,
+              "weights must be contiguous fp32 [T, k] on x's device");
+  const int64_t k = weights.size(1);
+  TORCH_CHECK(k >= 1 && k <= kMoeMaxTopK && k <= E,
+              "k must be in [1, min(8, E)], got ", k);
+  TORCH_CHECK(T * k <= kMoeMaxPairs, "too many (token, expert) pairs");
+  check_i32_on(expert_offsets, "expert_offsets", x.device(), E + 1);
+  check_i32_on(sorted_pairs, "sorted_pairs", x.device(), T * k);
+  auto y = torch::empty({T, H}, x.options());
+  if (T == 0) return y;
+  auto h = torch::empty({T * k, I}, x.options());
+  auto opart = torch::empty({T * k, H}, x.options().dtype(torch::kFloat32));
+  MoeFfnLaunch a;
+  a.y = y.data_ptr();
+  a.h = h.data_ptr();
+  a.opart = opart.data_ptr();
+  a.x = x.data_ptr();
+  a.w1 = w1.data_ptr();
+  a.w2 = w2.data_ptr();
+  a.weights = weights.data_ptr();
+  a.expert_offsets = expert_offsets.data_ptr();
+  a.sorted_pairs = sorted_pairs.data_ptr();
+  a.T = (int)T;
+  a.k = (int)k;
+  a.E = (int)E;
+  a.H = (int)H;
+  a.I = (int)I;
+  LAUNCH(launch_moe_ffn, a, current_stream());
+  return y;
+}
+
 // ---- fused seeded sampler (ops.sample) -----------------------------------
 // logits fp32 [n, V] contiguous; every per-row parameter is a device tensor
 // of length n, so nothing here reads a value back or synchronises.
@@ -1014,6 +1133,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("norm_weight"), py::arg("eps"), py::arg("force_splits") = 0);
   m.def("w8_dequant", &w8_dequant,
         "e4m3 [N, K] + int8 exponents [N] -> bf16 [N, K]");
+  m.def("moe_route", &moe_route,
+        "top-k routing + grouping by expert -> (ids, weights, "
+        "expert_offsets, sorted_pairs)");
+  m.def("moe_group", &moe_group,
+        "grouping of given ids by expert -> (expert_offsets, sorted_pairs)");
+  m.def("moe_ffn", &moe_ffn,
+        "grouped gate_up + SwiGLU, grouped down, weighted combine");
   m.def("sample", &sample,
         "seeded top-k/min-p/top-p Gumbel-max sampler -> (tokens, num_kept)");
   // gil_scoped_release on the IPC/copy entry points: mapping or launching

@@ -106,7 +106,34 @@ struct KvPeerCopyLaunch {
   long dst_chunk_stride_vec;
 };
 
+// The three launches behind the grouping of a mixture-of-experts FFN
+// (moe.hip): grouped gate_up + SwiGLU, grouped down, weighted combine.
+// 1 <= k <= 8, E <= 256, H % 256 == 0, I % 64 == 0.
+struct MoeFfnLaunch {
+  void* y;                     // [T, H] bf16
+  void* h;                     // [T * k, I] bf16 workspace, sorted order
+  void* opart;                 // [T * k, H] f32 workspace, pair order
+  const void* x;               // [T, H] bf16
+  const void* w1;              // [E, 2 * I, H] bf16: gate rows, then up rows
+  const void* w2;              // [E, H, I] bf16
+  const void* weights;         // [T, k] f32
+  const void* expert_offsets;  // [E + 1] int32
+  const void* sorted_pairs;    // [T * k] int32: pairs t * k + j by expert
+  int T, k, E, H, I;
+};
+
 extern "C" {
+
+// Top-k routing of bf16 logits [T, E] plus the grouping of the T * k pairs
+// by expert, one launch; ticket is one int32 that is zero between launches.
+// launch_moe_group is the grouping alone, for ids from elsewhere.
+hipError_t launch_moe_route(void* ids, void* weights, void* expert_offsets,
+                            void* sorted_pairs, void* ticket,
+                            const void* logits, int T, int E, int k,
+                            int renormalize, hipStream_t stream);
+hipError_t launch_moe_group(void* expert_offsets, void* sorted_pairs,
+                            const void* ids, int n, int E, hipStream_t stream);
+hipError_t launch_moe_ffn(const MoeFfnLaunch& a, hipStream_t stream);
 
 hipError_t launch_rmsnorm(void* out, void* input, const void* weight,
                           float eps, int tokens, int hidden,

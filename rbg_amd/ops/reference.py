@@ -436,3 +436,54 @@ def sample(logits: torch.Tensor, temperature: torch.Tensor,
                            int(pos[r]))
         toks[r], kept[r] = t, c
     return toks.to(logits.device), kept.to(logits.device)
+
+
+# ---------------------------------------------------------------------------
+# Mixture of experts (docs/FEATURES.md "Mixture of experts")
+# ---------------------------------------------------------------------------
+
+MOE_MAX_EXPERTS = 256
+MOE_MAX_TOP_K = 8
+
+
+def moe_route(router_logits: torch.Tensor, top_k: int,
+              renormalize: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(ids int32 [T, k], w fp32 [T, k]) of bf16 logits [T, E].  The k largest
+    logits by comparison, exact ties to the lower index, NaN as -inf, ordered
+    by descending logit; w = fp32 softmax over all E at the selected experts,
+    with `renormalize` divided by their fp32 sum added in slot order."""
+    x = router_logits.float()
+    x = torch.where(torch.isnan(x), torch.full_like(x, float("-inf")), x)
+    # a stable descending sort keeps equal logits in index order
+    order = torch.sort(x, dim=-1, descending=True, stable=True).indices
+    ids = order[:, :top_k]
+    w = torch.softmax(x, dim=-1).gather(1, ids)
+    if renormalize:
+        total = w[:, 0].clone()
+        for j in range(1, top_k):
+            total = total + w[:, j]
+        w = w / total.unsqueeze(1)
+    return ids.to(torch.int32).contiguous(), w.contiguous()
+
+
+def moe_ffn(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
+            ids: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """y bf16 [T, H] with the kernels' rounding points, one expert at a time:
+    g, u = x w1[e]^T in fp32 (not rounded), h = bf16(silu(g) * u),
+    o = h w2[e]^T in fp32, y[t] = bf16(sum_j w[t, j] * o[t, j]) in slot
+    order."""
+    T, H = x.shape
+    E, inter, k = w1.shape[0], w2.shape[2], ids.shape[1]
+    xf = x.float()
+    o = torch.zeros(T, k, H, dtype=torch.float32, device=x.device)
+    for e in range(E):
+        t_idx, j_idx = (ids == e).nonzero(as_tuple=True)
+        if t_idx.numel() == 0:
+            continue
+        gu = xf[t_idx] @ w1[e].float().t()
+        h = torch.nn.functional.silu(gu[:, :inter]) * gu[:, inter:]
+        o[t_idx, j_idx] = h.to(x.dtype).float() @ w2[e].float().t()
+    y = torch.zeros(T, H, dtype=torch.float32, device=x.device)
+    for j in range(k):
+        y = y + w[:, j:j + 1].float() * o[:, j]
+    return y.to(x.dtype)

@@ -30,6 +30,7 @@ HIP_SOURCES = [
     "silu_mul.hip",
     "skinny_gemm.hip",
     "skinny_gemm_w8.hip",
+    "moe.hip",
     "sampling.hip",
     "kv_peer_copy.hip",
     "allreduce.hip",
