@@ -226,9 +226,21 @@ def moe_route(router_logits: torch.Tensor, top_k: int,
         router_logits if router_logits.is_contiguous()
         else router_logits.contiguous(),
         _moe_ticket(router_logits.device), top_k, bool(renormalize))
-    # in [0, E) by construction: moe_ffn neither groups nor checks them again
+    # in [0, E) by construction: moe_ffn neither groups nor checks them again,
+    # unless ids was written to since (its version counter moved)
     ids._moe_group = (E, offsets, pairs)
+    ids._moe_group_version = _tensor_version(ids)
     return ids, w
+
+
+def _tensor_version(t: torch.Tensor):
+    """t._version, or None for an inference tensor (the model's forward runs
+    under torch.inference_mode, where tensors keep no version counter and an
+    in-place edit cannot be told; the model makes none)."""
+    try:
+        return t._version
+    except RuntimeError:
+        return None
 
 
 def moe_ffn(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
@@ -237,7 +249,8 @@ def moe_ffn(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
     weights w1 [E, 2I, H] (gate rows, then up rows) and w2 [E, H, I]:
     hip/moe.hip on a GPU, reference.moe_ffn on CPU tensors.  Everything is
     checked before anything is launched; ids that did not come from
-    moe_route are read back once for their range."""
+    moe_route, or were written to since, are read back once for their range
+    and grouped again."""
     for t, name, dt, nd in ((x, "x", torch.bfloat16, 2),
                             (w1, "w1", torch.bfloat16, 3),
                             (w2, "w2", torch.bfloat16, 3),
@@ -268,6 +281,9 @@ def moe_ffn(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
     if T == 0:
         return torch.empty_like(x)
     group = getattr(ids, "_moe_group", None)
+    if group is not None and (getattr(ids, "_moe_group_version", -1)
+                              != _tensor_version(ids)):
+        group = None            # ids was edited in place after moe_route
     if group is None or group[0] != E:
         lo, hi = int(ids.min()), int(ids.max())
         if lo < 0 or hi >= E:

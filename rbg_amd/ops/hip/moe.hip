@@ -511,6 +511,10 @@ __global__ void moe_combine_kernel(__hip_bfloat16* __restrict__ y,   // [T, H]
   const int H = hvec * 8;
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   for (int j = 0; j < k; ++j) {
+    // The product is rounded before it is added.  HIP's __fmul_rn / __fadd_rn
+    // are a plain * and + that the compiler's default contraction fused into
+    // v_fmac_f32 (one rounding); the pragma is what keeps them apart.
+#pragma clang fp contract(off)
     const float w = wts[t * k + j];
     const float* o = opart + (size_t)(t * k + j) * H + c;
     const float4 lo = *reinterpret_cast<const float4*>(o);
@@ -518,7 +522,7 @@ __global__ void moe_combine_kernel(__hip_bfloat16* __restrict__ y,   // [T, H]
     const float ov[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 #pragma unroll
     for (int q = 0; q < 8; ++q)
-      acc[q] = __fadd_rn(acc[q], __fmul_rn(w, ov[q]));   // two roundings
+      acc[q] = acc[q] + w * ov[q];                       // two roundings
   }
   Bf16x8U out;
 #pragma unroll

@@ -39,6 +39,56 @@ def test_route_groups_a_prefill_batch():
     check_grouping(ids, 8, 128)
 
 
+@pytest.mark.parametrize("E,k,T,renorm",
+                         mc.ROUTE_CASES_WIDE + mc.ROUTE_CASES_PAIRS)
+def test_route_wide(E, k, T, renorm):
+    """Expert counts off a multiple of 64 and E = 1, k = 3 / 6 / 7, and pair
+    counts either side of the sort's per-wave range."""
+    logits = mc.route_logits(E, T).cuda()
+    ids, w = ops.moe_route(logits, k, renorm)
+    mc.check_route(ids, w, logits, k, renorm)
+    check_grouping(ids, k, E)
+
+
+@pytest.mark.parametrize("E,k,T,hot", mc.ROUTE_CASES_SKEWED)
+def test_route_skewed(E, k, T, hot):
+    """Every pair (k = 1) or every token's first (k = 8) on one expert, the
+    first or the last: 64 peers in every ballot step of the sort."""
+    logits = mc.skewed_logits(E, T, hot).cuda()
+    ids, w = ops.moe_route(logits, k, True)
+    mc.check_route(ids, w, logits, k, True)
+    check_grouping(ids, k, E)
+    assert bool((ids[:, 0] == hot).all())
+
+
+@pytest.mark.parametrize("case", mc.FFN_CASES, ids=str)
+def test_ffn_combine_order(case):
+    """The combine's contract, bit for bit: f32 mul, f32 add, slot order."""
+    args = [t.cuda() for t in mc.ffn_case(case, "order")]
+    mc.check_ffn(args, "order", ops.moe_ffn(*args))
+
+
+def test_ffn_sees_an_edit_of_ids():
+    """ids edited in place after moe_route: moe_ffn regroups (and checks the
+    range again) instead of computing with the routing it no longer has."""
+    x, w1, w2, _, _ = (t.cuda() for t in mc.ffn_case(mc.FFN_CASES[1],
+                                                     "scaled"))
+    g = torch.Generator().manual_seed(5)
+    logits = torch.randn(x.shape[0], 8, generator=g).to(mc.BF16).cuda()
+    ids, w = ops.moe_route(logits, 2, True)
+    before = ops.moe_ffn(x, w1, w2, ids, w)
+    old = ids[0].tolist()
+    ids[0, 0] = next(e for e in range(8) if e not in old)
+    assert ids._moe_group_version != ids._version
+    after = ops.moe_ffn(x, w1, w2, ids, w)
+    assert torch.equal(after, ops.moe_ffn(x, w1, w2, ids.clone(), w))
+    assert not torch.equal(after[0], before[0])
+    assert torch.equal(after[1:], before[1:])
+    ids[0, 0] = 8
+    with pytest.raises(ValueError):
+        ops.moe_ffn(x, w1, w2, ids, w)
+
+
 @pytest.mark.parametrize("family", ("integer", "scaled"))
 @pytest.mark.parametrize("case", mc.FFN_CASES, ids=str)
 def test_ffn(case, family):
