@@ -37,7 +37,7 @@ def _check_stale() -> None:
     h = hashlib.sha256()
     hip_dir = os.path.join(here, "hip")
     for name in sorted(os.listdir(hip_dir)):
-        if name.endswith("_hip.hip"):
+        if name.endswith(("_hip.hip", "_hip.h")):
             continue
         if name.endswith((".hip", ".cpp", ".h")):
             with open(os.path.join(hip_dir, name), "rb") as f:
@@ -106,6 +106,26 @@ def dequantize_weight(w: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
     return reference.dequantize_weight_e4m3(w, e)
 
 
+def _use_skinny_gemm(x: torch.Tensor, w: torch.Tensor) -> bool:
+    # measured policy (profiles/sg_micro7_b*.json): the custom kernel wins
+    # on narrow-N shapes (o/down, N<=4096) at any decode batch, on mid-N
+    # (qkv, 6144) only up to M=64, and never on wide-N (gate_up 28672,
+    # where hipBLASLt already streams at ~6 TB/s)
+    return bool(SKINNY_GEMM and _on_gpu(x) and x.dim() == 2 and
+                x.dtype == torch.bfloat16 and 1 <= x.shape[0] <= 128 and
+                w.shape[0] % 32 == 0 and x.shape[1] % 512 == 0 and
+                (w.shape[0] <= 4608 or
+                 (x.shape[0] <= 64 and w.shape[0] <= 8192)))
+
+
+def _gemm_path(x: torch.Tensor, w: torch.Tensor, w_scale_log2) -> str:
+    """What linear() and linear_add_rmsnorm() run x w^T on: "w8"
+    (hip/skinny_gemm_w8.hip), "bf16" (hip/skinny_gemm.hip) or "library"."""
+    if _is_w8(w, w_scale_log2):
+        return "w8" if _on_gpu(x) and _use_skinny_gemm_w8(x, w) else "library"
+    return "bf16" if _use_skinny_gemm(x, w) else "library"
+
+
 def linear(x: torch.Tensor, w: torch.Tensor,
            w_scale_log2=None) -> torch.Tensor:
     """Projection GEMM with decode-shape dispatch: for M <= 128 rows the
@@ -116,27 +136,16 @@ def linear(x: torch.Tensor, w: torch.Tensor,
     An e4m3 `w` with its int8 exponents `w_scale_log2` is the bf16 weight
     dq = e4m3 * 2^e: M <= 128 takes hip/skinny_gemm_w8.hip at every N,
     anything else is dequantised (exactly) and goes to the library."""
-    if _is_w8(w, w_scale_log2):
-        if _on_gpu(x) and _use_skinny_gemm_w8(x, w):
-            return _require_hip().skinny_gemm_w8(
-                x if x.is_contiguous() else x.contiguous(), w, w_scale_log2)
-        return torch.nn.functional.linear(x, dequantize_weight(w, w_scale_log2))
-    # measured policy (profiles/sg_micro7_b*.json): the custom kernel wins
-    # on narrow-N shapes (o/down, N<=4096) at any decode batch, on mid-N
-    # (qkv, 6144) only up to M=64, and never on wide-N (gate_up 28672,
-    # where hipBLASLt already streams at ~6 TB/s)
-    if _use_skinny_gemm(x, w):
+    path = _gemm_path(x, w, w_scale_log2)
+    if path == "w8":
+        return _require_hip().skinny_gemm_w8(
+            x if x.is_contiguous() else x.contiguous(), w, w_scale_log2)
+    if path == "bf16":
         return _require_hip().skinny_gemm(
             x if x.is_contiguous() else x.contiguous(), w)
+    if w_scale_log2 is not None:
+        w = dequantize_weight(w, w_scale_log2)
     return torch.nn.functional.linear(x, w)
-
-
-def _use_skinny_gemm(x: torch.Tensor, w: torch.Tensor) -> bool:
-    return bool(SKINNY_GEMM and _on_gpu(x) and x.dim() == 2 and
-                x.dtype == torch.bfloat16 and 1 <= x.shape[0] <= 128 and
-                w.shape[0] % 32 == 0 and x.shape[1] % 512 == 0 and
-                (w.shape[0] <= 4608 or
-                 (x.shape[0] <= 64 and w.shape[0] <= 8192)))
 
 
 def linear_add_rmsnorm(x: torch.Tensor, w: torch.Tensor,
@@ -147,19 +156,16 @@ def linear_add_rmsnorm(x: torch.Tensor, w: torch.Tensor,
     linear() would take the custom GEMM, the split-K partials are folded
     inside the norm kernel instead of by a reduce launch of their own
     (hip/rmsnorm.hip, NORM_FOLD_ADD).  w_scale_log2: as in linear()."""
-    if _is_w8(w, w_scale_log2):
-        if _on_gpu(x) and _use_skinny_gemm_w8(x, w):
-            return _require_hip().skinny_gemm_w8_add_rmsnorm(
-                x if x.is_contiguous() else x.contiguous(), w, w_scale_log2,
-                residual, norm_weight, eps)
-        h = linear(x, w, w_scale_log2)
-        fused_add_rmsnorm(h, residual, norm_weight, eps)
-        return h
-    if _use_skinny_gemm(x, w):
+    path = _gemm_path(x, w, w_scale_log2)
+    if path == "w8":
+        return _require_hip().skinny_gemm_w8_add_rmsnorm(
+            x if x.is_contiguous() else x.contiguous(), w, w_scale_log2,
+            residual, norm_weight, eps)
+    if path == "bf16":
         return _require_hip().skinny_gemm_add_rmsnorm(
             x if x.is_contiguous() else x.contiguous(), w, residual,
             norm_weight, eps)
-    h = linear(x, w)
+    h = linear(x, w) if w_scale_log2 is None else linear(x, w, w_scale_log2)
     fused_add_rmsnorm(h, residual, norm_weight, eps)
     return h
 

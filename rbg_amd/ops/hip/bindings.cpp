@@ -537,8 +537,8 @@ bool skinny_gemm_supported(int64_t M, int64_t N, int64_t K) {
   return M >= 1 && M <= 256 && (N % 32) == 0 && (K % 256) == 0;
 }
 
-// The 64-column-panel kernel (skinny_gemm_wide_kernel): 8 waves over
-// 4 row groups of at most 2 m-tiles, whole 64-column panels.
+// The 64-column-panel kernel (skinny_gemm_tile.h) on bf16 weights: 8 waves
+// over 4 row groups of at most 2 m-tiles, whole 64-column panels.
 bool skinny_gemm_wide_supported(int64_t M, int64_t N) {
   return M >= 1 && M <= 128 && (N % 64) == 0;
 }
@@ -555,10 +555,39 @@ static int pick_gemm_panel(int64_t M, int64_t N) {
 
 namespace {
 
+// What the bf16 and the e4m3 GEMM launch share once their operands are
+// checked: the split count (the bf16 GEMM's policy for both, so that both
+// engines split alike) and the output it implies.  With splits > 1 the f32
+// partials [splits, M, N] go to `ws` for the caller to fold, with splits == 1
+// the bf16 result goes to `c`; the other of *cp / *wsp stays null.  `k_unit`
+// is what the caller's message calls the split count that K must hold.
+int plan_gemm_splits(const torch::Tensor& a, int64_t N, int64_t force_splits,
+                     const char* k_unit, torch::Tensor& c, torch::Tensor& ws,
+                     void** cp, void** wsp) {
+  const int64_t M = a.size(0), K = a.size(1);
+  // only SPLITS 1/2/4/8 are instantiated, and each split's k range must be
+  // whole 256-k groups (an even, >= 4 step count): anything else would
+  // launch a kernel whose grid and workspace disagree with its k span
+  TORCH_CHECK(force_splits == 0 || force_splits == 1 || force_splits == 2 ||
+                  force_splits == 4 || force_splits == 8,
+              "force_splits must be 0 (auto), 1, 2, 4 or 8");
+  const int splits = force_splits > 0 ? (int)force_splits
+                                      : pick_gemm_splits((int)N, (int)K);
+  TORCH_CHECK(K >= 256 && K % (splits * 256) == 0, "K must be a multiple of ",
+              k_unit, " * 256");
+  if (splits > 1) {
+    ws = torch::empty({splits, M, N}, a.options().dtype(torch::kFloat32));
+    *wsp = ws.data_ptr();
+  } else {
+    c = torch::empty({M, N}, a.options());
+    *cp = c.data_ptr();
+  }
+  return splits;
+}
+
 // Shape, dtype, device and contiguity checks shared by skinny_gemm and
-// skinny_gemm_add_rmsnorm, then the GEMM launch.  Returns the split count;
-// with splits > 1 the f32 partials [splits, M, N] are left in `ws` for the
-// caller to fold, with splits == 1 the bf16 result is in `c`.
+// skinny_gemm_add_rmsnorm, then the GEMM launch.  Returns the split count
+// and leaves the result in `c` or `ws` as plan_gemm_splits says.
 int skinny_gemm_launch(const torch::Tensor& a, const torch::Tensor& w,
                        int64_t force_splits, int64_t panel, torch::Tensor& c,
                        torch::Tensor& ws) {
@@ -569,30 +598,15 @@ int skinny_gemm_launch(const torch::Tensor& a, const torch::Tensor& w,
   const int64_t M = a.size(0), K = a.size(1), N = w.size(0);
   TORCH_CHECK(w.size(1) == K, "K mismatch");
   TORCH_CHECK(skinny_gemm_supported(M, N, K), "unsupported skinny shape");
-  // only SPLITS 1/2/4/8 are instantiated, and each split's k range must be
-  // whole 256-k groups (an even, >= 4 step count): anything else would
-  // launch a kernel whose grid and workspace disagree with its k span
-  TORCH_CHECK(force_splits == 0 || force_splits == 1 || force_splits == 2 ||
-                  force_splits == 4 || force_splits == 8,
-              "force_splits must be 0 (auto), 1, 2, 4 or 8");
-  TORCH_CHECK(force_splits == 0 || K % (force_splits * 256) == 0,
-              "K must be a multiple of force_splits * 256");
   TORCH_CHECK(panel == 0 || panel == 32 || panel == 64,
               "panel must be 0 (auto), 32 or 64");
   TORCH_CHECK(panel != 64 || skinny_gemm_wide_supported(M, N),
               "panel 64 needs M <= 128 and N % 64 == 0");
-  const int splits = force_splits > 0 ? (int)force_splits
-                                      : pick_gemm_splits((int)N, (int)K);
-  if (panel == 0) panel = pick_gemm_panel(M, N);
   void* cp = nullptr;
   void* wsp = nullptr;
-  if (splits > 1) {
-    ws = torch::empty({splits, M, N}, a.options().dtype(torch::kFloat32));
-    wsp = ws.data_ptr();
-  } else {
-    c = torch::empty({M, N}, a.options());
-    cp = c.data_ptr();
-  }
+  const int splits =
+      plan_gemm_splits(a, N, force_splits, "force_splits", c, ws, &cp, &wsp);
+  if (panel == 0) panel = pick_gemm_panel(M, N);
   if (panel == 64)
     LAUNCH(launch_skinny_gemm_wide, cp, wsp, a.data_ptr(), w.data_ptr(),
            (int)M, (int)N, (int)K, splits, current_stream());
@@ -682,23 +696,10 @@ int skinny_gemm_w8_launch(const torch::Tensor& a, const torch::Tensor& w8,
   TORCH_CHECK(w8.size(1) == K, "K mismatch");
   TORCH_CHECK(M >= 1 && M <= 128, "M must be in [1, 128], got ", M);
   TORCH_CHECK(N >= 64 && N % 64 == 0, "N must be a multiple of 64, got ", N);
-  TORCH_CHECK(force_splits == 0 || force_splits == 1 || force_splits == 2 ||
-                  force_splits == 4 || force_splits == 8,
-              "force_splits must be 0 (auto), 1, 2, 4 or 8");
-  // the bf16 GEMM's policy, so that both engines split alike
-  const int splits = force_splits > 0 ? (int)force_splits
-                                      : pick_gemm_splits((int)N, (int)K);
-  TORCH_CHECK(K >= 256 && K % (splits * 256) == 0,
-              "K must be a multiple of splits * 256");
   void* cp = nullptr;
   void* wsp = nullptr;
-  if (splits > 1) {
-    ws = torch::empty({splits, M, N}, a.options().dtype(torch::kFloat32));
-    wsp = ws.data_ptr();
-  } else {
-    c = torch::empty({M, N}, a.options());
-    cp = c.data_ptr();
-  }
+  const int splits =
+      plan_gemm_splits(a, N, force_splits, "splits", c, ws, &cp, &wsp);
   LAUNCH(launch_skinny_gemm_w8, cp, wsp, a.data_ptr(), w8.data_ptr(),
          e.data_ptr(), (int)M, (int)N, (int)K, splits, current_stream());
   return splits;

@@ -62,7 +62,7 @@
     __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
 #endif
 
-#include "common.h"
+#include "skinny_gemm_tile.h"   // lds_frag
 #include "launch.h"
 
 namespace {
@@ -290,12 +290,6 @@ constexpr int MG_RED_BYTES = 2 * MG_MT * 2 * 256 * 4;
 constexpr int MG_LDS_BYTES =
     MG_STAGE_BYTES > MG_RED_BYTES ? MG_STAGE_BYTES : MG_RED_BYTES;
 
-DEV_INLINE bf16x8 mg_frag(const __hip_bfloat16* p) {
-  union { uint4 u; bf16x8 v; } cvt;
-  cvt.u = *reinterpret_cast<const uint4*>(p);
-  return cvt.v;
-}
-
 // One pass of one workgroup: acc[mt][i] += W tile (t0 + 2i) x A tile mt over
 // nsteps 64-k steps.  wb0/wb1 are this thread's two W pieces (stage rows srow
 // and 32 + srow), ab0/ab1 its A pieces (tile rows srow and 32 + srow, clamped
@@ -340,11 +334,11 @@ DEV_INLINE void mg_pass(__hip_bfloat16* stage,
 
   const int kf = k_slice * 32 + gslice * 8;
   auto compute = [&](const __hip_bfloat16* st) {
-    const bf16x8 wf0 = mg_frag(&st[(t0 * 16 + gl) * MG_PITCH + kf]);
-    const bf16x8 wf1 = mg_frag(&st[((t0 + 2) * 16 + gl) * MG_PITCH + kf]);
+    const bf16x8 wf0 = lds_frag(&st[(t0 * 16 + gl) * MG_PITCH + kf]);
+    const bf16x8 wf1 = lds_frag(&st[((t0 + 2) * 16 + gl) * MG_PITCH + kf]);
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
-      const bf16x8 af = mg_frag(&st[(64 + mt * 16 + gl) * MG_PITCH + kf]);
+      const bf16x8 af = lds_frag(&st[(64 + mt * 16 + gl) * MG_PITCH + kf]);
       acc[mt][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf0, af, acc[mt][0],
                                                            0, 0, 0);
       acc[mt][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf1, af, acc[mt][1],
