@@ -49,10 +49,19 @@ class ModelConfig:
     moe_intermediate_size: int = 0
     norm_topk_prob: bool = True
 
-    def check_moe(self, tp_size: int = 1, weight_dtype: str = "bf16") -> None:
+    def check_moe(self, tp_size: int = 1, weight_dtype: str = "bf16",
+                  expert_weight_dtype: str = "bf16") -> None:
         """Raises ValueError for an expert configuration the kernels do not
-        serve (hip/moe.hip)."""
+        serve (hip/moe.hip).  expert_weight_dtype is the experts' own option
+        (docs/FEATURES.md "FP8 experts"); weight_dtype, the dense
+        projections', stays bf16 for a model with experts."""
+        if expert_weight_dtype not in WEIGHT_DTYPES:
+            raise ValueError("unknown expert_weight_dtype %r (one of %s)" % (
+                expert_weight_dtype, ", ".join(WEIGHT_DTYPES)))
         if self.num_experts == 0:
+            if expert_weight_dtype != "bf16":
+                raise ValueError("expert_weight_dtype %r needs a model with "
+                                 "experts" % expert_weight_dtype)
             return
         E, k = self.num_experts, self.num_experts_per_tok
         if tp_size > 1:
@@ -167,6 +176,10 @@ class EngineConfig:
     # qkv, o, gate_up and down of every layer as e4m3 bytes with one
     # power-of-two exponent per output row
     weight_dtype: str = "bf16"
+    # Expert weights of a mixture-of-experts model (docs/FEATURES.md "FP8
+    # experts"): "fp8_e4m3" holds w1 and w2 of every layer as e4m3 bytes with
+    # one power-of-two exponent per expert output row
+    expert_weight_dtype: str = "bf16"
 
     def __post_init__(self) -> None:
         if self.weight_dtype not in WEIGHT_DTYPES:
@@ -179,7 +192,8 @@ class EngineConfig:
                 self.page_size != 16 or self.model.head_dim != 128):
             raise ValueError("prefill_kv_read 'paged' needs page_size 16 and "
                              "head_dim 128")
-        self.model.check_moe(self.tp_size, self.weight_dtype)
+        self.model.check_moe(self.tp_size, self.weight_dtype,
+                             self.expert_weight_dtype)
         kv_element_size(self.kv_cache_dtype)       # raises on an unknown name
         for name in ("kv_k_scale_log2", "kv_v_scale_log2"):
             e = getattr(self, name)

@@ -35,7 +35,8 @@ class ModelRunner:
         torch.manual_seed(cfg.seed)
         self.pp = pp or PPContext()
         self.model = LlamaForCausalLM(cfg.model, self.device, tp, pp=self.pp,
-                                      weight_dtype=cfg.weight_dtype)
+                                      weight_dtype=cfg.weight_dtype,
+                                      expert_weight_dtype=cfg.expert_weight_dtype)
         self.cache = PagedKVCache(cfg, self.device,
                                   num_layers=self.model.num_local_layers)
         self.max_pages_per_seq = (cfg.max_seq_len + cfg.page_size - 1) // \

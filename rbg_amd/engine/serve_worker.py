@@ -44,8 +44,12 @@ def _engine_cfg(ctx: WorkerContext) -> EngineConfig:
     model = ModelConfig.preset(args.get("model", "llama-3-8b"))
     device = "cuda" if (torch.cuda.is_available() and ctx.gpu_ids != []) \
         else args.get("device", "cpu")
+    expert_weight_dtype = str(args.get("expert_weight_dtype", "bf16"))
     if device == "cpu" and args.get("model", "") not in ("tiny",):
+        had_experts = model.num_experts > 0
         model = ModelConfig.preset(args.get("cpu_model", "tiny"))
+        if had_experts and model.num_experts == 0:
+            expert_weight_dtype = "bf16"    # a dense stand-in has no experts
     return EngineConfig(
         model=model, device=device,
         page_size=int(args.get("page_size", 16)),
@@ -61,6 +65,7 @@ def _engine_cfg(ctx: WorkerContext) -> EngineConfig:
         kv_v_scale_log2=int(args.get("kv_v_scale_log2", 0)),
         prefill_kv_read=str(args.get("prefill_kv_read", "gather")),
         weight_dtype=str(args.get("weight_dtype", "bf16")),
+        expert_weight_dtype=expert_weight_dtype,
     )
 
 
@@ -404,6 +409,7 @@ class ServeWorker:
                 self.engine.runner.cache.signature(),
                 num_pages=self.engine.runner.cache.num_pages)
             out["weight_dtype"] = self.cfg.weight_dtype
+            out["expert_weight_dtype"] = self.cfg.expert_weight_dtype
             if self._xfer_stats["pushes"]:
                 xs = dict(self._xfer_stats)
                 xs["gb_per_s"] = round(

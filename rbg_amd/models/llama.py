@@ -373,9 +373,12 @@ class LlamaMLP(nn.Module):
 class MoEBlock(nn.Module):
     """The FFN of a mixture-of-experts layer (cfg.num_experts > 0): a bf16
     router and num_experts SwiGLU experts, num_experts_per_tok per token
-    (docs/FEATURES.md "Mixture of experts")."""
+    (docs/FEATURES.md "Mixture of experts").  fp8_experts: w1 and w2 are the
+    e4m3 quantisation of the bf16 draws, one exponent per expert output row
+    (w1_scale [E, 2I], w2_scale [E, H]); the router stays bf16."""
 
-    def __init__(self, cfg: ModelConfig, device, dtype, gen):
+    def __init__(self, cfg: ModelConfig, device, dtype, gen,
+                 fp8_experts: bool = False):
         super().__init__()
         E, H, I = cfg.num_experts, cfg.hidden_size, cfg.moe_intermediate_size
         self.top_k = cfg.num_experts_per_tok
@@ -386,19 +389,34 @@ class MoEBlock(nn.Module):
             return nn.Parameter(t.normal_(0.0, 0.02, generator=gen),
                                 requires_grad=False)
 
+        def quantized(p):
+            w8, e = ops.quantize_weight_e4m3(p.data.view(-1, p.shape[2]))
+            return (nn.Parameter(w8.view(p.shape), requires_grad=False),
+                    nn.Parameter(e.view(p.shape[:2]), requires_grad=False))
+
         self.w_router = draw(E, H)
         self.w1 = draw(E, 2 * I, H)      # gate rows [0, I), up rows [I, 2I)
+        self.w1_scale = None
+        if fp8_experts:
+            self.w1, self.w1_scale = quantized(self.w1)
         self.w2 = draw(E, H, I)
+        self.w2_scale = None
+        if fp8_experts:
+            self.w2, self.w2_scale = quantized(self.w2)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         ids, w = ops.moe_route(ops.linear(x, self.w_router), self.top_k,
                                self.renormalize)
-        return ops.moe_ffn(x, self.w1, self.w2, ids, w)
+        if self.w1_scale is None:       # the call a bf16 block always made
+            return ops.moe_ffn(x, self.w1, self.w2, ids, w)
+        return ops.moe_ffn(x, self.w1, self.w2, ids, w, self.w1_scale,
+                           self.w2_scale)
 
 
 class LlamaLayer(nn.Module):
     def __init__(self, cfg: ModelConfig, layer_idx: int, tp: TPContext,
-                 device, dtype, gen, fp8_weights: bool = False):
+                 device, dtype, gen, fp8_weights: bool = False,
+                 fp8_experts: bool = False):
         super().__init__()
         # layer_idx here is the KV-cache index LOCAL to this PP stage; the
         # weight generator is already seeded by the GLOBAL layer index
@@ -408,7 +426,7 @@ class LlamaLayer(nn.Module):
         # unfused layer does: no down_proj for linear_add_rmsnorm to fuse into
         self.moe = cfg.num_experts > 0
         if self.moe:
-            self.mlp = MoEBlock(cfg, device, dtype, gen)
+            self.mlp = MoEBlock(cfg, device, dtype, gen, fp8_experts)
         else:
             self.mlp = LlamaMLP(cfg, tp, device, dtype, gen, fp8_weights)
         self.input_norm = nn.Parameter(
@@ -458,7 +476,8 @@ class LlamaLayer(nn.Module):
 class LlamaForCausalLM(nn.Module):
     def __init__(self, cfg: ModelConfig, device: torch.device,
                  tp: Optional[TPContext] = None, base_seed: int = 1234,
-                 pp: Optional[PPContext] = None, weight_dtype: str = "bf16"):
+                 pp: Optional[PPContext] = None, weight_dtype: str = "bf16",
+                 expert_weight_dtype: str = "bf16"):
         super().__init__()
         if weight_dtype not in ops.WEIGHT_DTYPES:
             raise ValueError("unknown weight_dtype %r (one of %s)" % (
@@ -466,9 +485,11 @@ class LlamaForCausalLM(nn.Module):
         # "fp8_e4m3": the four projections of every layer are e4m3 with
         # per-row exponents; embed, the norms and lm_head stay bf16
         self.weight_dtype = weight_dtype
+        # "fp8_e4m3": w1 and w2 of every MoE block likewise (MoEBlock)
+        self.expert_weight_dtype = expert_weight_dtype
         self.cfg = cfg
         self.tp = tp or TPContext()
-        cfg.check_moe(self.tp.size, weight_dtype)
+        cfg.check_moe(self.tp.size, weight_dtype, expert_weight_dtype)
         self.pp = pp or PPContext()
         self.base_seed = base_seed
         self.device = device
@@ -497,7 +518,8 @@ class LlamaForCausalLM(nn.Module):
                 requires_grad=False)
         self.layers = nn.ModuleList([
             LlamaLayer(cfg, i - self.layer_start, self.tp, device, dtype,
-                       _gen(1 + i), weight_dtype == "fp8_e4m3")
+                       _gen(1 + i), weight_dtype == "fp8_e4m3",
+                       expert_weight_dtype == "fp8_e4m3")
             for i in range(self.layer_start, self.layer_end)])
         self.link_norm_fusion(self.tp.size == 1)
         self.final_norm = None
@@ -511,7 +533,8 @@ class LlamaForCausalLM(nn.Module):
         self.cos_sin = ops.build_cos_sin_table(
             cfg.head_dim, cfg.max_position, cfg.rope_theta,
             device=device)
-        if weight_dtype != "bf16" and device.type == "cuda":
+        if (weight_dtype, expert_weight_dtype) != ("bf16", "bf16") and \
+                device.type == "cuda":
             # the bf16 and fp32 temporaries of quantisation are several times
             # the bytes that stay: hand them back before the KV pool is sized
             # from the free memory
@@ -573,7 +596,8 @@ class LlamaForCausalLM(nn.Module):
         any captured hipGraphs keep their addresses)."""
         fresh = LlamaForCausalLM(self.cfg, self.device, self.tp,
                                  base_seed=seed, pp=self.pp,
-                                 weight_dtype=self.weight_dtype)
+                                 weight_dtype=self.weight_dtype,
+                                 expert_weight_dtype=self.expert_weight_dtype)
         with torch.no_grad():
             for p, q in zip(self.parameters(), fresh.parameters()):
                 p.copy_(q)

@@ -250,16 +250,28 @@ def _tensor_version(t: torch.Tensor):
 
 
 def moe_ffn(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
-            ids: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+            ids: torch.Tensor, w: torch.Tensor, w1_scale_log2=None,
+            w2_scale_log2=None) -> torch.Tensor:
     """y bf16 [T, H] = sum_j w[t, j] * FFN_{ids[t, j]}(x[t]) with expert
     weights w1 [E, 2I, H] (gate rows, then up rows) and w2 [E, H, I]:
     hip/moe.hip on a GPU, reference.moe_ffn on CPU tensors.  Everything is
     checked before anything is launched; ids that did not come from
     moe_route, or were written to since, are read back once for their range
-    and grouped again."""
+    and grouped again.
+
+    e4m3 w1 and w2 with their int8 exponents w1_scale_log2 [E, 2I] and
+    w2_scale_log2 [E, H] (ops.quantize_weight_e4m3 of the weights viewed
+    [E * rows, K]) are the bf16 experts dq = e4m3 * 2^e: on a GPU the e4m3
+    instantiation of the grouped GEMMs, bit for bit the bf16 one on dq."""
+    if w1.dtype != w2.dtype:
+        raise ValueError("w1 and w2 must have one dtype, got %s and %s" % (
+            w1.dtype, w2.dtype))
+    w8 = _is_w8(w1, w1_scale_log2)
+    _is_w8(w2, w2_scale_log2)
+    wdt = FP8 if w8 else torch.bfloat16
     for t, name, dt, nd in ((x, "x", torch.bfloat16, 2),
-                            (w1, "w1", torch.bfloat16, 3),
-                            (w2, "w2", torch.bfloat16, 3),
+                            (w1, "w1", wdt, 3),
+                            (w2, "w2", wdt, 3),
                             (ids, "ids", torch.int32, 2),
                             (w, "w", torch.float32, 2)):
         if t.dtype != dt or t.dim() != nd:
@@ -284,6 +296,15 @@ def moe_ffn(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
         raise ValueError("moe_ffn needs E <= %d, k <= min(%d, E), H %% 256 == "
                          "0 and I %% 64 == 0, got E = %d, k = %d, H = %d, I = "
                          "%d" % (MOE_MAX_EXPERTS, MOE_MAX_TOP_K, E, k, H, I))
+    if w8:
+        for e, name, rows in ((w1_scale_log2, "w1_scale_log2", 2 * I),
+                              (w2_scale_log2, "w2_scale_log2", H)):
+            if (e.dtype != torch.int8 or tuple(e.shape) != (E, rows) or
+                    not e.is_contiguous() or e.device != x.device):
+                raise ValueError("%s must be contiguous int8 %s on %s, got "
+                                 "%s %s on %s" % (name, (E, rows), x.device,
+                                                  tuple(e.shape), e.dtype,
+                                                  e.device))
     if T == 0:
         return torch.empty_like(x)
     group = getattr(ids, "_moe_group", None)
@@ -298,7 +319,14 @@ def moe_ffn(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
         if _on_gpu(x):
             group = (E,) + tuple(_require_hip().moe_group(ids, E))
     if not _on_gpu(x):
+        if w8:
+            w1, w2 = (reference.dequantize_weight_e4m3(
+                t.view(-1, t.shape[2]), e.view(-1)).view(t.shape)
+                for t, e in ((w1, w1_scale_log2), (w2, w2_scale_log2)))
         return reference.moe_ffn(x, w1, w2, ids, w)
+    if w8:
+        return _require_hip().moe_ffn(x, w1, w2, w, group[1], group[2],
+                                      w1_scale_log2, w2_scale_log2)
     return _require_hip().moe_ffn(x, w1, w2, w, group[1], group[2])
 
 

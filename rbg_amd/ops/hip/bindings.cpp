@@ -779,12 +779,40 @@ void check_i32_on(const torch::Tensor& t, const char* name,
 }
 
 // The expert weights of one layer, w1 [E, 2I, H] and w2 [E, H, I] on x's
-// device, for the shapes the grouped GEMMs serve.
+// device, for the shapes the grouped GEMMs serve: both bf16 and no exponents,
+// or both e4m3 with e1 int8 [E, 2I] and e2 int8 [E, H] (docs/FEATURES.md "FP8
+// experts").
 void check_moe_experts(const torch::Tensor& x, const torch::Tensor& w1,
-                       const torch::Tensor& w2) {
+                       const torch::Tensor& w2,
+                       const c10::optional<torch::Tensor>& e1,
+                       const c10::optional<torch::Tensor>& e2) {
   check_bf16_contig(x, "x");
-  check_bf16_contig(w1, "w1");
-  check_bf16_contig(w2, "w2");
+  TORCH_CHECK(w1.scalar_type() == w2.scalar_type(),
+              "w1 and w2 must have one dtype");
+  if (w1.scalar_type() == torch::kFloat8_e4m3fn) {
+    TORCH_CHECK(e1.has_value() && e2.has_value(),
+                "e4m3 experts need w1_scale_log2 and w2_scale_log2");
+    const torch::Tensor* w[2] = {&w1, &w2};
+    const torch::Tensor* e[2] = {&*e1, &*e2};
+    for (int i = 0; i < 2; ++i) {
+      TORCH_CHECK(w[i]->is_cuda() && w[i]->is_contiguous() &&
+                      (uintptr_t)w[i]->data_ptr() % 16 == 0,
+                  "an e4m3 expert weight must be contiguous on GPU");
+      TORCH_CHECK(e[i]->scalar_type() == torch::kChar &&
+                      e[i]->is_contiguous() && e[i]->dim() == 2 &&
+                      w[i]->dim() == 3 && e[i]->size(0) == w[i]->size(0) &&
+                      e[i]->size(1) == w[i]->size(1) &&
+                      e[i]->device() == x.device() &&
+                      (uintptr_t)e[i]->data_ptr() % 4 == 0,
+                  "an expert scale must be contiguous int8 [E, rows of its "
+                  "weight] on x's device");
+    }
+  } else {
+    TORCH_CHECK(!e1.has_value() && !e2.has_value(),
+                "a scale was given for experts that are not e4m3");
+    check_bf16_contig(w1, "w1");
+    check_bf16_contig(w2, "w2");
+  }
   TORCH_CHECK(x.dim() == 2, "x must be [T, H]");
   TORCH_CHECK(w1.dim() == 3 && w2.dim() == 3,
               "w1 must be [E, 2I, H] and w2 [E, H, I]");
@@ -841,11 +869,14 @@ std::vector<torch::Tensor> moe_group(torch::Tensor ids, int64_t E) {
   return {offsets, sorted};
 }
 
-// y bf16 [T, H] from the grouping of moe_route / moe_group.
+// y bf16 [T, H] from the grouping of moe_route / moe_group.  e4m3 w1 and w2
+// come with their int8 exponents and stand for dq = e4m3 * 2^e[expert, row].
 torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor w1, torch::Tensor w2,
                       torch::Tensor weights, torch::Tensor expert_offsets,
-                      torch::Tensor sorted_pairs) {
-  check_moe_experts(x, w1, w2);
+                      torch::Tensor sorted_pairs,
+                      c10::optional<torch::Tensor> w1_scale_log2,
+                      c10::optional<torch::Tensor> w2_scale_log2) {
+  check_moe_experts(x, w1, w2, w1_scale_log2, w2_scale_log2);
   const int64_t T = x.size(0), H = x.size(1), E = w1.size(0), I = w2.size(2);
   TORCH_CHECK(weights.is_cuda() && weights.device() == x.device() &&
                   weights.scalar_type() == torch::kFloat32 &&
@@ -877,6 +908,10 @@ torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor w1, torch::Tensor w2,
   a.E = (int)E;
   a.H = (int)H;
   a.I = (int)I;
+  if (w1_scale_log2.has_value()) {
+    a.w1_exp = w1_scale_log2->data_ptr();
+    a.w2_exp = w2_scale_log2->data_ptr();
+  }
   LAUNCH(launch_moe_ffn, a, current_stream());
   return y;
 }
@@ -1140,7 +1175,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_group", &moe_group,
         "grouping of given ids by expert -> (expert_offsets, sorted_pairs)");
   m.def("moe_ffn", &moe_ffn,
-        "grouped gate_up + SwiGLU, grouped down, weighted combine");
+        "grouped gate_up + SwiGLU, grouped down, weighted combine; e4m3 w1 "
+        "and w2 take their int8 per-row exponents",
+        py::arg("x"), py::arg("w1"), py::arg("w2"), py::arg("weights"),
+        py::arg("expert_offsets"), py::arg("sorted_pairs"),
+        py::arg("w1_scale_log2") = py::none(),
+        py::arg("w2_scale_log2") = py::none());
   m.def("sample", &sample,
         "seeded top-k/min-p/top-p Gumbel-max sampler -> (tokens, num_kept)");
   // gil_scoped_release on the IPC/copy entry points: mapping or launching

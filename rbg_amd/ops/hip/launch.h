@@ -108,18 +108,22 @@ struct KvPeerCopyLaunch {
 
 // The three launches behind the grouping of a mixture-of-experts FFN
 // (moe.hip): grouped gate_up + SwiGLU, grouped down, weighted combine.
-// 1 <= k <= 8, E <= 256, H % 256 == 0, I % 64 == 0.
+// 1 <= k <= 8, E <= 256, H % 256 == 0, I % 64 == 0.  w1_exp and w2_exp are
+// both null (bf16 w1, w2) or both set: w1 and w2 are then e4m3 bytes and the
+// exponents one int8 per expert output row, 4-byte aligned.
 struct MoeFfnLaunch {
   void* y;                     // [T, H] bf16
   void* h;                     // [T * k, I] bf16 workspace, sorted order
   void* opart;                 // [T * k, H] f32 workspace, pair order
   const void* x;               // [T, H] bf16
-  const void* w1;              // [E, 2 * I, H] bf16: gate rows, then up rows
-  const void* w2;              // [E, H, I] bf16
+  const void* w1;              // [E, 2 * I, H]: gate rows, then up rows
+  const void* w2;              // [E, H, I]
   const void* weights;         // [T, k] f32
   const void* expert_offsets;  // [E + 1] int32
   const void* sorted_pairs;    // [T * k] int32: pairs t * k + j by expert
   int T, k, E, H, I;
+  const void* w1_exp = nullptr;  // [E, 2 * I] int8
+  const void* w2_exp = nullptr;  // [E, H] int8
 };
 
 extern "C" {

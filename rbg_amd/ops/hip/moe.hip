@@ -51,6 +51,32 @@
 // tile.  Rows past the expert's count are clamped to a live row on the way
 // in and never stored.
 //
+// e4m3 experts (docs/FEATURES.md "FP8 experts"): w1 / w2 as e4m3 bytes with
+// one int8 exponent per expert output row, dq = e4m3 * 2^e.  Kernels 2 and 3
+// have a second instantiation (WT = uint8_t) that differs in how W travels:
+//   stage = 128 k, two 64-k steps per barrier.  W's 64 rows x 128 B are two
+//           16-byte pieces per thread, 8 lanes per 128-byte row segment (the
+//           bf16 request shape at half the rows' bytes); A's 16 MT rows x
+//           256 B are MT pieces per thread, 16 lanes per row.
+//   LDS   = W stays BYTES: a lane's fragment is one 8-byte read and four
+//           v_cvt_scalef32_pk_bf16_fp8 at scale 1 (exact).  Each W fragment
+//           is read by one lane per pass, so nothing is converted twice and
+//           W's LDS write traffic halves.  Row pitch 144 B (36 banks: the 16
+//           rows of a tile start 4 banks apart in a permutation of 0 .. 60
+//           and the two 8-byte reads of a row pair fill the 4: conflict-free;
+//           the 16-byte writes see what the bf16 stage's 144 B pitch sees).
+//           A rows are 128 + 8 bf16.  Two buffers = a ring four 64-k steps
+//           deep, 53 248 B at MT = 4 (three workgroups per CU).
+//   tail  = an odd step count (K = 192) ends in half a stage: the pieces
+//           past K are re-reads of the row's last piece (never past the
+//           tensor) and the second 64-k step is skipped.
+//   chain = unchanged: k-slice s takes [32 s, 32 s + 32) of step 2 j, then
+//           of step 2 j + 1, so every output is the two chains above on
+//           e4m3 -> bf16 values, and 2^e[row] multiplies the folded f32 sum
+//           (before SiLU for gate and up, each with its own exponent).  That
+//           is the bf16 kernel's result on dq bit for bit: a power of two
+//           commutes with every rounding on the way.
+//
 // No atomics on floats anywhere; the one atomic is the integer ticket (and
 // integer LDS counters inside the sort, whose totals do not depend on order).
 // All global writes are plain vector stores.
@@ -369,20 +395,140 @@ DEV_INLINE void mg_pass(__hip_bfloat16* stage,
 #undef MG_LD
 }
 
+// e4m3 W: 128-k stages, W as bytes in LDS (the file header has the layout)
+constexpr int M8_KSTAGE = 128;
+constexpr int M8_WPITCH = M8_KSTAGE + 16;    // bytes per staged W row
+constexpr int M8_APITCH = M8_KSTAGE + 8;     // bf16 per staged A row
+constexpr int M8_W_BYTES = 64 * M8_WPITCH;
+constexpr int M8_STAGE_BYTES =
+    2 * (M8_W_BYTES + 16 * MG_MT * M8_APITCH * 2);
+constexpr int M8_LDS_BYTES =
+    M8_STAGE_BYTES > MG_RED_BYTES ? M8_STAGE_BYTES : MG_RED_BYTES;
+
+// mg_pass for e4m3 W.  wb0/wb1: this thread's W rows (stage rows srow and
+// 32 + srow) at k = 0; ab0..ab3: its A rows (tile rows arow + 16 i, clamped
+// by the caller; ab1..ab3 are read at MT = 4 only) at k = 0.  The thread's
+// piece within a stage is added here, clamped to the row's last piece.
+template <int MT>
+DEV_INLINE void mg_pass_w8(unsigned char* stage,
+                           const uint8_t* __restrict__ wb0,
+                           const uint8_t* __restrict__ wb1,
+                           const __hip_bfloat16* __restrict__ ab0,
+                           const __hip_bfloat16* __restrict__ ab1,
+                           const __hip_bfloat16* __restrict__ ab2,
+                           const __hip_bfloat16* __restrict__ ab3,
+                           const int nsteps, f32x4 (&acc)[MT][2]) {
+  constexpr int BUF = M8_W_BYTES + 16 * MT * M8_APITCH * 2;
+  constexpr bool A4 = MT > 1;                // four A pieces per thread
+  static_assert(MT == 1 || MT == 4, "one or four A pieces per thread");
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int gl = lane & 15, gslice = lane >> 4;
+  const int t0 = wave & 1, k_slice = wave >> 1;
+  const int srow = tid >> 3, wchk = (tid & 7) * 16;   // W: bytes
+  const int arow = tid >> 4, achk = (tid & 15) * 8;   // A: bf16
+  const int K = nsteps * MG_KSTEP;
+  const int nstages = (nsteps + 1) >> 1;
+
+  uint4 w00, w01, a00, a01 = {}, a02 = {}, a03 = {};
+  uint4 w10, w11, a10, a11 = {}, a12 = {}, a13 = {};
+#define M8_LD(p, kb) (*reinterpret_cast<const uint4*>((p) + (kb)))
+#define M8_ISSUE(stg, wa, wb, aa, ab, ac, ad)                               \
+  do {                                                                      \
+    const int kb = min(stg, nstages - 1) * M8_KSTAGE;                       \
+    const int ka = min(kb + achk, K - 8);                                   \
+    const int kw = min(kb + wchk, K - 16);                                  \
+    aa = M8_LD(ab0, ka);                                                    \
+    if (A4) {                                                               \
+      ab = M8_LD(ab1, ka);                                                  \
+      ac = M8_LD(ab2, ka);                                                  \
+      ad = M8_LD(ab3, ka);                                                  \
+    }                                                                       \
+    wa = M8_LD(wb0, kw);                                                    \
+    wb = M8_LD(wb1, kw);                                                    \
+  } while (0)
+#define M8_WST(st, row)                                                     \
+  reinterpret_cast<uint4*>((st) + (row) * M8_WPITCH + wchk)
+#define M8_AST(st, row)                                                     \
+  reinterpret_cast<uint4*>((st) + M8_W_BYTES +                              \
+                           ((row) * M8_APITCH + achk) * 2)
+#define M8_WRITE(st, wa, wb, aa, ab, ac, ad)                                \
+  do {                                                                      \
+    *M8_WST(st, srow) = wa;                                                 \
+    *M8_WST(st, 32 + srow) = wb;                                            \
+    *M8_AST(st, arow) = aa;                                                 \
+    if (A4) {                                                               \
+      *M8_AST(st, 16 + arow) = ab;                                          \
+      *M8_AST(st, 32 + arow) = ac;                                          \
+      *M8_AST(st, 48 + arow) = ad;                                          \
+    }                                                                       \
+  } while (0)
+
+  // stage `stg` of buffer st: its first 64-k step, and its second unless the
+  // step count is odd and this is the last stage
+  auto compute = [&](const unsigned char* st, const int stg) {
+    const __hip_bfloat16* ast =
+        reinterpret_cast<const __hip_bfloat16*>(st + M8_W_BYTES);
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      if (half == 1 && 2 * stg + 1 >= nsteps) break;
+      const int kf = half * MG_KSTEP + k_slice * 32 + gslice * 8;
+      const bf16x8 wf0 = lds_frag_w8(&st[(t0 * 16 + gl) * M8_WPITCH + kf]);
+      const bf16x8 wf1 =
+          lds_frag_w8(&st[((t0 + 2) * 16 + gl) * M8_WPITCH + kf]);
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) {
+        const bf16x8 af = lds_frag(&ast[(mt * 16 + gl) * M8_APITCH + kf]);
+        acc[mt][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            wf0, af, acc[mt][0], 0, 0, 0);
+        acc[mt][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            wf1, af, acc[mt][1], 0, 0, 0);
+      }
+    }
+  };
+
+  unsigned char* buf0 = stage;
+  unsigned char* buf1 = stage + BUF;
+  M8_ISSUE(0, w00, w01, a00, a01, a02, a03);
+  M8_ISSUE(1, w10, w11, a10, a11, a12, a13);
+  M8_WRITE(buf0, w00, w01, a00, a01, a02, a03);
+  M8_ISSUE(2, w00, w01, a00, a01, a02, a03);
+  for (int stg = 0; stg < nstages; stg += 2) {
+    __syncthreads();
+    compute(buf0, stg);
+    M8_WRITE(buf1, w10, w11, a10, a11, a12, a13);
+    M8_ISSUE(stg + 3, w10, w11, a10, a11, a12, a13);
+    if (stg + 1 >= nstages) break;           // odd stage count
+    __syncthreads();
+    compute(buf1, stg + 1);
+    M8_WRITE(buf0, w00, w01, a00, a01, a02, a03);
+    M8_ISSUE(stg + 4, w00, w01, a00, a01, a02, a03);
+  }
+#undef M8_WRITE
+#undef M8_AST
+#undef M8_WST
+#undef M8_ISSUE
+#undef M8_LD
+}
+
 struct MoeGemmArgs {
   void* out;                  // GATE_UP: h bf16 [TK, N]; else opart f32 [TK, N]
   const __hip_bfloat16* a;    // GATE_UP: x [T, K]; else h [TK, K]
-  const __hip_bfloat16* w;    // GATE_UP: w1 [E, 2N, K]; else w2 [E, N, K]
+  const void* w;              // GATE_UP: w1 [E, 2N, K]; else w2 [E, N, K]
   const int* offsets;         // [E + 1]
   const int* sorted;          // [TK]
   int TK, k, K, N, panels;
+  const int8_t* wexp;         // e4m3 w: [E, 2N] or [E, N] exponents; else null
 };
 
 // All passes of one expert's rows at MT row tiles per pass.
-template <int MT, bool GATE_UP>
+// WT: __hip_bfloat16, or uint8_t for e4m3 W, whose exponents for this panel's
+// stage rows start at we (gate rows; the up rows' are g.N further).
+template <int MT, bool GATE_UP, typename WT>
 DEV_INLINE void mg_expert(const MoeGemmArgs& g, unsigned char* smem,
-                          const __hip_bfloat16* wb0, const __hip_bfloat16* wb1,
+                          const WT* wb0, const WT* wb1, const int8_t* we,
                           const int off, const int n, const int panel) {
+  constexpr bool W8 = sizeof(WT) == 1;
   __hip_bfloat16* stage = reinterpret_cast<__hip_bfloat16*>(smem);
   float* red = reinterpret_cast<float*>(smem);
   const int tid = threadIdx.x;
@@ -411,8 +557,22 @@ DEV_INLINE void mg_expert(const MoeGemmArgs& g, unsigned char* smem,
       acc[mt][0] = {0.f, 0.f, 0.f, 0.f};
       acc[mt][1] = {0.f, 0.f, 0.f, 0.f};
     }
-    mg_pass<MT>(stage, wb0, wb1, g.a + ar0 * g.K + schk, g.a + ar1 * g.K + schk,
-                nsteps, acc);
+    if constexpr (W8) {
+      // tile rows arow + 16 i of this pass, 16 lanes per row
+      const __hip_bfloat16* ab[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int s = off + r0 + min((tid >> 4) + 16 * i, live - 1);
+        const size_t ar = GATE_UP ? (size_t)(min(max(g.sorted[s], 0),
+                                                 g.TK - 1) / g.k)
+                                  : (size_t)s;
+        ab[i] = g.a + ar * g.K;
+      }
+      mg_pass_w8<MT>(smem, wb0, wb1, ab[0], ab[1], ab[2], ab[3], nsteps, acc);
+    } else {
+      mg_pass<MT>(stage, wb0, wb1, g.a + ar0 * g.K + schk,
+                  g.a + ar1 * g.K + schk, nsteps, acc);
+    }
 
     // fold the two k-slices: slice 1 -> LDS -> slice 0 adds and stores
     __syncthreads();
@@ -440,6 +600,19 @@ DEV_INLINE void mg_expert(const MoeGemmArgs& g, unsigned char* smem,
           for (int r = 0; r < 4; ++r)
             v[i][r] = acc[mt][i][r] +
                       red[((t0 * MT + mt) * 2 + i) * 256 + r * 64 + lane];
+        if constexpr (W8) {
+          // 2^e of W rows 4 * gslice + r: four int8 of one word per tile
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            const int row = (GATE_UP ? i * g.N + t0 * 16
+                                     : (t0 + 2 * i) * 16) + gslice * 4;
+            const unsigned word =
+                *reinterpret_cast<const unsigned*>(we + row);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)   // byte r, sign-extended
+              v[i][r] *= w8_exp2i((int)(word << (24 - 8 * r)) >> 24);
+          }
+        }
         if (GATE_UP) {
           union { __hip_bfloat16 e[4]; uint2 u; } hv;
 #pragma unroll
@@ -466,28 +639,35 @@ DEV_INLINE void mg_expert(const MoeGemmArgs& g, unsigned char* smem,
   }
 }
 
-template <bool GATE_UP>
+template <bool GATE_UP, typename WT>
 __global__ __launch_bounds__(MG_NT) void moe_gemm_kernel(const MoeGemmArgs g) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[MG_LDS_BYTES];
+  constexpr bool W8 = sizeof(WT) == 1;
+  __shared__ __attribute__((aligned(16))) unsigned char
+      smem[W8 ? M8_LDS_BYTES : MG_LDS_BYTES];
   const int e = blockIdx.x / g.panels;
   const int panel = blockIdx.x % g.panels;
   const int off = min(max(g.offsets[e], 0), g.TK);
   const int n = min(max(g.offsets[e + 1], off), g.TK) - off;
   if (n <= 0) return;
-  const int srow = threadIdx.x >> 3, schk = (threadIdx.x & 7) * 8;
-  const __hip_bfloat16* wb0;
-  const __hip_bfloat16* wb1;
+  // (an e4m3 pass adds the thread's piece itself: it clamps it to the row)
+  const int srow = threadIdx.x >> 3, schk = W8 ? 0 : (threadIdx.x & 7) * 8;
+  const WT* w = reinterpret_cast<const WT*>(g.w);
+  const WT* wb0;
+  const WT* wb1;
+  const int8_t* we = nullptr;
   if (GATE_UP) {              // stage rows [0, 32) gate, [32, 64) up
-    wb0 = g.w + ((size_t)e * 2 * g.N + panel * 32 + srow) * g.K + schk;
+    wb0 = w + ((size_t)e * 2 * g.N + panel * 32 + srow) * g.K + schk;
     wb1 = wb0 + (size_t)g.N * g.K;
+    if (W8) we = g.wexp + (size_t)e * 2 * g.N + panel * 32;
   } else {
-    wb0 = g.w + ((size_t)e * g.N + panel * 64 + srow) * g.K + schk;
+    wb0 = w + ((size_t)e * g.N + panel * 64 + srow) * g.K + schk;
     wb1 = wb0 + (size_t)32 * g.K;
+    if (W8) we = g.wexp + (size_t)e * g.N + panel * 64;
   }
   if (n <= 16)
-    mg_expert<1, GATE_UP>(g, smem, wb0, wb1, off, n, panel);
+    mg_expert<1, GATE_UP>(g, smem, wb0, wb1, we, off, n, panel);
   else
-    mg_expert<MG_MT, GATE_UP>(g, smem, wb0, wb1, off, n, panel);
+    mg_expert<MG_MT, GATE_UP>(g, smem, wb0, wb1, we, off, n, panel);
 }
 
 // ---------------------------------------------------------------------------
@@ -555,15 +735,25 @@ hipError_t launch_moe_ffn(const MoeFfnLaunch& a, hipStream_t stream) {
   if (a.T < 1 || a.k < 1 || a.k > 8 || a.E < 1 || a.E > MR_EMAX ||
       a.H < 256 || a.H % 256 || a.I < 64 || a.I % 64)
     return hipErrorInvalidValue;
+  const bool w8 = a.w1_exp != nullptr;
+  if (w8 != (a.w2_exp != nullptr)) return hipErrorInvalidValue;
   const int TK = a.T * a.k;
-  MoeGemmArgs gu = {a.h, (const __hip_bfloat16*)a.x,
-                    (const __hip_bfloat16*)a.w1, (const int*)a.expert_offsets,
-                    (const int*)a.sorted_pairs, TK, a.k, a.H, a.I, a.I / 32};
-  moe_gemm_kernel<true><<<dim3(a.E * gu.panels), dim3(MG_NT), 0, stream>>>(gu);
-  MoeGemmArgs dn = {a.opart, (const __hip_bfloat16*)a.h,
-                    (const __hip_bfloat16*)a.w2, (const int*)a.expert_offsets,
-                    (const int*)a.sorted_pairs, TK, a.k, a.I, a.H, a.H / 64};
-  moe_gemm_kernel<false><<<dim3(a.E * dn.panels), dim3(MG_NT), 0, stream>>>(dn);
+  const MoeGemmArgs gu = {a.h, (const __hip_bfloat16*)a.x, a.w1,
+                          (const int*)a.expert_offsets,
+                          (const int*)a.sorted_pairs, TK, a.k, a.H, a.I,
+                          a.I / 32, (const int8_t*)a.w1_exp};
+  const MoeGemmArgs dn = {a.opart, (const __hip_bfloat16*)a.h, a.w2,
+                          (const int*)a.expert_offsets,
+                          (const int*)a.sorted_pairs, TK, a.k, a.I, a.H,
+                          a.H / 64, (const int8_t*)a.w2_exp};
+  const dim3 ggu(a.E * gu.panels), gdn(a.E * dn.panels), block(MG_NT);
+  if (w8) {
+    moe_gemm_kernel<true, uint8_t><<<ggu, block, 0, stream>>>(gu);
+    moe_gemm_kernel<false, uint8_t><<<gdn, block, 0, stream>>>(dn);
+  } else {
+    moe_gemm_kernel<true, __hip_bfloat16><<<ggu, block, 0, stream>>>(gu);
+    moe_gemm_kernel<false, __hip_bfloat16><<<gdn, block, 0, stream>>>(dn);
+  }
   const int hvec = a.H / 8;
   const long total = (long)a.T * hvec;
   moe_combine_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0,

@@ -15,6 +15,41 @@ DEV_INLINE bf16x8 lds_frag(const __hip_bfloat16* p) {
   return cvt.v;
 }
 
+// Four e4m3 bytes -> four bf16, two per v_cvt_scalef32_pk_bf16_fp8 at scale 1
+// (exact: e4m3's four significant bits and exponent range fit a bf16).
+DEV_INLINE uint2 w8_cvt4(unsigned w) {
+  union { bf16x2 v; unsigned u; } lo, hi;
+  lo.v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false);
+  hi.v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true);
+  uint2 r;
+  r.x = lo.u;
+  r.y = hi.u;
+  return r;
+}
+
+// 16 e4m3 bytes -> 16 bf16 as two 16-byte pieces (elements 0-7, 8-15)
+DEV_INLINE void w8_cvt16(const uint4& b, uint4& lo, uint4& hi) {
+  const uint2 a0 = w8_cvt4(b.x), a1 = w8_cvt4(b.y);
+  const uint2 a2 = w8_cvt4(b.z), a3 = w8_cvt4(b.w);
+  lo = make_uint4(a0.x, a0.y, a1.x, a1.y);
+  hi = make_uint4(a2.x, a2.y, a3.x, a3.y);
+}
+
+// MFMA fragment from 8 staged e4m3 bytes of one row: one 8-byte LDS read,
+// converted by the lane that feeds it to the MFMA
+DEV_INLINE bf16x8 lds_frag_w8(const uint8_t* p) {
+  const uint2 b = *reinterpret_cast<const uint2*>(p);
+  const uint2 lo = w8_cvt4(b.x), hi = w8_cvt4(b.y);
+  union { uint4 u; bf16x8 v; } cvt;
+  cvt.u = make_uint4(lo.x, lo.y, hi.x, hi.y);
+  return cvt.v;
+}
+
+// 2^e as f32 bits; |e| <= 64 keeps the exponent field normal
+DEV_INLINE float w8_exp2i(int e) {
+  return __uint_as_float((unsigned)(e + 127) << 23);
+}
+
 // One kernel per split count the GEMMs are instantiated for.  KERNEL is a
 // template over (row tiles, SPLITS, ...); grid, block, stream and splits are
 // the launcher's.

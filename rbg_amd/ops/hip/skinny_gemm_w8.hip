@@ -49,30 +49,7 @@
 
 namespace {
 
-// Four e4m3 bytes -> four bf16, two per v_cvt_scalef32_pk_bf16_fp8 at scale 1
-// (exact: e4m3's four significant bits and exponent range fit a bf16).
-DEV_INLINE uint2 w8_cvt4(unsigned w) {
-  union { bf16x2 v; unsigned u; } lo, hi;
-  lo.v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false);
-  hi.v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true);
-  uint2 r;
-  r.x = lo.u;
-  r.y = hi.u;
-  return r;
-}
-
-// 16 e4m3 bytes -> 16 bf16 as two 16-byte pieces (elements 0-7, 8-15)
-DEV_INLINE void w8_cvt16(const uint4& b, uint4& lo, uint4& hi) {
-  const uint2 a0 = w8_cvt4(b.x), a1 = w8_cvt4(b.y);
-  const uint2 a2 = w8_cvt4(b.z), a3 = w8_cvt4(b.w);
-  lo = make_uint4(a0.x, a0.y, a1.x, a1.y);
-  hi = make_uint4(a2.x, a2.y, a3.x, a3.y);
-}
-
-// 2^e as f32 bits; |e| <= 64 keeps the exponent field normal
-DEV_INLINE float w8_exp2i(int e) {
-  return __uint_as_float((unsigned)(e + 127) << 23);
-}
+// (w8_cvt4 / w8_cvt16 / w8_exp2i: skinny_gemm_tile.h, shared with moe.hip)
 
 // e4m3 weights for the 64-column kernel (skinny_gemm_tile.h): 128-k stages, a
 // W register is 16 e4m3 bytes and goes to LDS as two bf16 pieces, column n's

@@ -140,10 +140,15 @@ def engine_rows(args):
     B, ctx, new = 128, 2048, 4 + args.engine_rounds * args.engine_steps + 8
     engines = {}
     variants = {"bf16": {}, "fp8": dict(kv_cache_dtype="fp8_e4m3")}
+    model = "llama-3-8b"
     if args.engine_weights:       # FP8 projection weights over a bf16 pool
         variants = {"bf16": {}, "fp8w": dict(weight_dtype="fp8_e4m3")}
+    if args.engine_experts:       # FP8 expert weights of the MoE model
+        model = "qwen3-30b-a3b"
+        variants = {"bf16": {},
+                    "fp8_experts": dict(expert_weight_dtype="fp8_e4m3")}
     for name, kw in variants.items():
-        cfg = EngineConfig(model=ModelConfig.preset("llama-3-8b"),
+        cfg = EngineConfig(model=ModelConfig.preset(model),
                            device="cuda", max_batch_size=B,
                            max_seq_len=ctx + new + 16,
                            kv_pool_tokens=B * (ctx + new + 32),
@@ -171,9 +176,20 @@ def engine_rows(args):
             times[name].append((time.perf_counter() - t0) * 1e6 /
                                args.engine_steps)
     rows = []
+    hbm = torch.cuda.get_device_properties(0).total_memory
     for name, eng in engines.items():
+        model_bytes = sum(p.numel() * p.element_size()
+                          for p in eng.runner.model.parameters())
+        page_bytes = (eng.cfg.model.kv_bytes_per_token(eng.cfg.kv_cache_dtype)
+                      * eng.cfg.page_size)
         rows.append(dict(kind="engine_decode_step", dtype=name, batch=B,
-                         ctx=ctx, kv_pages=eng.runner.cache.num_pages,
+                         ctx=ctx, model=model,
+                         model_gb=round(model_bytes / 1e9, 2),
+                         # what is left of the device beside the weights, at
+                         # the default gpu_memory_utilization (computed)
+                         kv_pages_at_085=int((hbm - model_bytes) * 0.85
+                                             // page_bytes),
+                         kv_pages=eng.runner.cache.num_pages,
                          pool_gb=round(eng.runner.cache.kv.numel() *
                                        eng.runner.cache.kv.element_size()
                                        / 1e9, 2),
@@ -191,12 +207,15 @@ def main() -> None:
     ap.add_argument("--no-engine", action="store_true")
     ap.add_argument("--engine-weights", action="store_true",
                     help="engine rows only: bf16 against fp8_e4m3 weights")
+    ap.add_argument("--engine-experts", action="store_true",
+                    help="engine rows only: qwen3-30b-a3b, bf16 against "
+                         "fp8_e4m3 expert weights")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     assert ops.HAVE_HIP, ops._hip_err
-    results = [] if args.engine_weights else (decode_rows(args) +
-                                              store_rows(args))
+    engine_only = args.engine_weights or args.engine_experts
+    results = [] if engine_only else (decode_rows(args) + store_rows(args))
     if not args.no_engine:
         results += engine_rows(args)
     if args.out:

@@ -47,15 +47,80 @@ def time_calls(fn, n_layers, rounds, warmup=2):
     return times
 
 
+def w8_main(args, dev, shape):
+    """--w8: ops.moe_ffn with bf16 against e4m3 experts (the quantisation of
+    the same weights), the two alternating call by call over the cold layer
+    sets.  TB/s counts each dtype's own weight bytes of the experts touched
+    (exponents included)."""
+    E, K, H, I = shape
+    g = torch.Generator(device=dev).manual_seed(0)
+    rnd = lambda *s: torch.randn(*s, device=dev, generator=g)
+    sets = []
+    for _ in range(args.layers):
+        w1 = (rnd(E, 2 * I, H) * 0.02).bfloat16()
+        w2 = (rnd(E, H, I) * 0.02).bfloat16()
+        q = [ops.quantize_weight_e4m3(w.view(-1, w.shape[2])) for w in (w1, w2)]
+        sets.append({"bf16": (w1, w2, None, None),
+                     "e4m3": (q[0][0].view(w1.shape), q[1][0].view(w2.shape),
+                              q[0][1].view(E, 2 * I), q[1][1].view(E, H))})
+    per_expert = {"bf16": 3 * I * H * 2, "e4m3": 3 * I * H + 2 * I + H}
+    out = {"shape": {"E": E, "k": K, "H": H, "I": I}, "layers": args.layers}
+    for T in (int(t) for t in args.tokens.split(",")):
+        x = (rnd(T, H) * 0.5).bfloat16()
+        routed = [ops.moe_route(rnd(T, E).bfloat16(), K, True)
+                  for _ in range(args.layers)]
+        touched = [ids.unique().numel() for ids, _ in routed]
+
+        def call(name, i):
+            w1, w2, e1, e2 = sets[i][name]
+            if e1 is None:
+                return ops.moe_ffn(x, w1, w2, *routed[i])
+            return ops.moe_ffn(x, w1, w2, *routed[i], e1, e2)
+
+        times = {"bf16": [], "e4m3": []}
+        for r in range(2 + args.rounds):
+            for i in range(args.layers):
+                for name in times:
+                    s = torch.cuda.Event(enable_timing=True)
+                    e = torch.cuda.Event(enable_timing=True)
+                    s.record()
+                    call(name, i)
+                    e.record()
+                    torch.cuda.synchronize()
+                    if r >= 2:
+                        times[name].append(s.elapsed_time(e) * 1e3)
+        row = {"experts_touched": touched[0],
+               "cold": sum(touched) * per_expert["e4m3"] >= 2 * L3_BYTES}
+        for name, ts in times.items():
+            med = statistics.median(ts)
+            row[name + "_us"] = round(med, 1)
+            row[name + "_us_min_max"] = [round(min(ts), 1), round(max(ts), 1)]
+            row[name + "_weight_TBps"] = round(
+                sum(touched) / len(touched) * per_expert[name] / med / 1e6, 2)
+        row["e4m3_over_bf16"] = round(row["e4m3_us"] / row["bf16_us"], 3)
+        out["T%d" % T] = row
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tokens", default="1,16,128,2048")
     ap.add_argument("--layers", type=int, default=8)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=None, help="also write the JSON here")
+    ap.add_argument("--w8", action="store_true",
+                    help="bf16 against e4m3 experts instead of hip against "
+                         "the loop")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     E, K, H, I = 128, 8, 2048, 768
+    if args.w8:
+        text = json.dumps(w8_main(args, dev, (E, K, H, I)), indent=1)
+        print(text, flush=True)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     g = torch.Generator(device=dev).manual_seed(0)
     rnd = lambda *s: torch.randn(*s, device=dev, generator=g)
     w1 = [(rnd(E, 2 * I, H) * 0.02).bfloat16() for _ in range(args.layers)]
