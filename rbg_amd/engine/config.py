@@ -16,6 +16,8 @@ KV_CACHE_DTYPES = ("bf16", "fp8_e4m3")
 KV_SCALE_LOG2_MIN, KV_SCALE_LOG2_MAX = -16, 16
 PREFILL_KV_READS = ("gather", "paged")
 WEIGHT_DTYPES = ("bf16", "fp8_e4m3")
+# the experts' own option also has MXFP4 (docs/FEATURES.md "MXFP4 experts")
+EXPERT_WEIGHT_DTYPES = WEIGHT_DTYPES + ("mxfp4",)
 
 
 def kv_element_size(kv_cache_dtype: str) -> int:
@@ -53,11 +55,11 @@ class ModelConfig:
                   expert_weight_dtype: str = "bf16") -> None:
         """Raises ValueError for an expert configuration the kernels do not
         serve (hip/moe.hip).  expert_weight_dtype is the experts' own option
-        (docs/FEATURES.md "FP8 experts"); weight_dtype, the dense
-        projections', stays bf16 for a model with experts."""
-        if expert_weight_dtype not in WEIGHT_DTYPES:
+        (docs/FEATURES.md "FP8 experts", "MXFP4 experts"); weight_dtype, the
+        dense projections', stays bf16 for a model with experts."""
+        if expert_weight_dtype not in EXPERT_WEIGHT_DTYPES:
             raise ValueError("unknown expert_weight_dtype %r (one of %s)" % (
-                expert_weight_dtype, ", ".join(WEIGHT_DTYPES)))
+                expert_weight_dtype, ", ".join(EXPERT_WEIGHT_DTYPES)))
         if self.num_experts == 0:
             if expert_weight_dtype != "bf16":
                 raise ValueError("expert_weight_dtype %r needs a model with "
@@ -178,7 +180,8 @@ class EngineConfig:
     weight_dtype: str = "bf16"
     # Expert weights of a mixture-of-experts model (docs/FEATURES.md "FP8
     # experts"): "fp8_e4m3" holds w1 and w2 of every layer as e4m3 bytes with
-    # one power-of-two exponent per expert output row
+    # one power-of-two exponent per expert output row; "mxfp4" ("MXFP4
+    # experts") as e2m1 codes, two per byte, with one exponent per 32 k
     expert_weight_dtype: str = "bf16"
 
     def __post_init__(self) -> None:

@@ -373,12 +373,15 @@ class LlamaMLP(nn.Module):
 class MoEBlock(nn.Module):
     """The FFN of a mixture-of-experts layer (cfg.num_experts > 0): a bf16
     router and num_experts SwiGLU experts, num_experts_per_tok per token
-    (docs/FEATURES.md "Mixture of experts").  fp8_experts: w1 and w2 are the
-    e4m3 quantisation of the bf16 draws, one exponent per expert output row
-    (w1_scale [E, 2I], w2_scale [E, H]); the router stays bf16."""
+    (docs/FEATURES.md "Mixture of experts").  expert_weight_dtype "fp8_e4m3":
+    w1 and w2 are the e4m3 quantisation of the bf16 draws, one exponent per
+    expert output row (w1_scale [E, 2I], w2_scale [E, H]); "mxfp4": their
+    e2m1 codes, two per byte ([E, 2I, H/2], [E, H, I/2]), one exponent per 32
+    k (w1_scale [E, 2I, H/32], w2_scale [E, H, I/32]).  The router stays
+    bf16."""
 
     def __init__(self, cfg: ModelConfig, device, dtype, gen,
-                 fp8_experts: bool = False):
+                 expert_weight_dtype: str = "bf16"):
         super().__init__()
         E, H, I = cfg.num_experts, cfg.hidden_size, cfg.moe_intermediate_size
         self.top_k = cfg.num_experts_per_tok
@@ -390,18 +393,26 @@ class MoEBlock(nn.Module):
                                 requires_grad=False)
 
         def quantized(p):
-            w8, e = ops.quantize_weight_e4m3(p.data.view(-1, p.shape[2]))
-            return (nn.Parameter(w8.view(p.shape), requires_grad=False),
-                    nn.Parameter(e.view(p.shape[:2]), requires_grad=False))
+            rows = p.data.view(-1, p.shape[2])
+            if expert_weight_dtype == "mxfp4":
+                q, e = ops.quantize_weight_mxfp4(rows)
+            else:
+                q, e = ops.quantize_weight_e4m3(rows)
+            return (nn.Parameter(q.view(*p.shape[:2], -1),
+                                 requires_grad=False),
+                    nn.Parameter(e.view(*p.shape[:2], *e.shape[1:]),
+                                 requires_grad=False))
+
+        quantise = expert_weight_dtype != "bf16"
 
         self.w_router = draw(E, H)
         self.w1 = draw(E, 2 * I, H)      # gate rows [0, I), up rows [I, 2I)
         self.w1_scale = None
-        if fp8_experts:
+        if quantise:
             self.w1, self.w1_scale = quantized(self.w1)
         self.w2 = draw(E, H, I)
         self.w2_scale = None
-        if fp8_experts:
+        if quantise:
             self.w2, self.w2_scale = quantized(self.w2)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -416,7 +427,7 @@ class MoEBlock(nn.Module):
 class LlamaLayer(nn.Module):
     def __init__(self, cfg: ModelConfig, layer_idx: int, tp: TPContext,
                  device, dtype, gen, fp8_weights: bool = False,
-                 fp8_experts: bool = False):
+                 expert_weight_dtype: str = "bf16"):
         super().__init__()
         # layer_idx here is the KV-cache index LOCAL to this PP stage; the
         # weight generator is already seeded by the GLOBAL layer index
@@ -426,7 +437,8 @@ class LlamaLayer(nn.Module):
         # unfused layer does: no down_proj for linear_add_rmsnorm to fuse into
         self.moe = cfg.num_experts > 0
         if self.moe:
-            self.mlp = MoEBlock(cfg, device, dtype, gen, fp8_experts)
+            self.mlp = MoEBlock(cfg, device, dtype, gen,
+                                expert_weight_dtype)
         else:
             self.mlp = LlamaMLP(cfg, tp, device, dtype, gen, fp8_weights)
         self.input_norm = nn.Parameter(
@@ -485,7 +497,8 @@ class LlamaForCausalLM(nn.Module):
         # "fp8_e4m3": the four projections of every layer are e4m3 with
         # per-row exponents; embed, the norms and lm_head stay bf16
         self.weight_dtype = weight_dtype
-        # "fp8_e4m3": w1 and w2 of every MoE block likewise (MoEBlock)
+        # "fp8_e4m3": w1 and w2 of every MoE block likewise; "mxfp4": as e2m1
+        # codes with one exponent per 32 k (MoEBlock)
         self.expert_weight_dtype = expert_weight_dtype
         self.cfg = cfg
         self.tp = tp or TPContext()
@@ -519,7 +532,7 @@ class LlamaForCausalLM(nn.Module):
         self.layers = nn.ModuleList([
             LlamaLayer(cfg, i - self.layer_start, self.tp, device, dtype,
                        _gen(1 + i), weight_dtype == "fp8_e4m3",
-                       expert_weight_dtype == "fp8_e4m3")
+                       expert_weight_dtype)
             for i in range(self.layer_start, self.layer_end)])
         self.link_norm_fusion(self.tp.size == 1)
         self.final_norm = None

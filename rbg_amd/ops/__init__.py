@@ -75,6 +75,9 @@ FP8 = torch.float8_e4m3fn
 WEIGHT_DTYPES = reference.WEIGHT_DTYPES
 quantize_weight_e4m3 = reference.quantize_weight_e4m3
 dequantize_weight_e4m3 = reference.dequantize_weight_e4m3
+EXPERT_WEIGHT_DTYPES = reference.EXPERT_WEIGHT_DTYPES
+quantize_weight_mxfp4 = reference.quantize_weight_mxfp4
+dequantize_weight_mxfp4 = reference.dequantize_weight_mxfp4
 
 
 def _is_w8(w: torch.Tensor, w_scale_log2) -> bool:
@@ -262,13 +265,28 @@ def moe_ffn(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
     e4m3 w1 and w2 with their int8 exponents w1_scale_log2 [E, 2I] and
     w2_scale_log2 [E, H] (ops.quantize_weight_e4m3 of the weights viewed
     [E * rows, K]) are the bf16 experts dq = e4m3 * 2^e: on a GPU the e4m3
-    instantiation of the grouped GEMMs, bit for bit the bf16 one on dq."""
+    instantiation of the grouped GEMMs, bit for bit the bf16 one on dq.
+
+    uint8 w1 [E, 2I, H/2] and w2 [E, H, I/2] are MXFP4 (docs/FEATURES.md
+    "MXFP4 experts"): two e2m1 codes per byte with int8 exponents per 32 k,
+    w1_scale_log2 [E, 2I, H/32] and w2_scale_log2 [E, H, I/32]
+    (ops.quantize_weight_mxfp4 of the weights viewed [E * rows, K]).  They
+    are the bf16 experts dq = e2m1 * 2^e: the MXFP4 instantiation on a GPU,
+    again bit for bit the bf16 one on dq."""
     if w1.dtype != w2.dtype:
         raise ValueError("w1 and w2 must have one dtype, got %s and %s" % (
             w1.dtype, w2.dtype))
-    w8 = _is_w8(w1, w1_scale_log2)
-    _is_w8(w2, w2_scale_log2)
-    wdt = FP8 if w8 else torch.bfloat16
+    w4 = w1.dtype == torch.uint8
+    if w4:
+        for e in (w1_scale_log2, w2_scale_log2):
+            if e is None or e.dim() != 3:
+                raise ValueError("an MXFP4 weight needs its scale_log2, the "
+                                 "3-D int8 exponents per 32 k")
+        w8, wdt = False, torch.uint8
+    else:
+        w8 = _is_w8(w1, w1_scale_log2)
+        _is_w8(w2, w2_scale_log2)
+        wdt = FP8 if w8 else torch.bfloat16
     for t, name, dt, nd in ((x, "x", torch.bfloat16, 2),
                             (w1, "w1", wdt, 3),
                             (w2, "w2", wdt, 3),
@@ -284,7 +302,15 @@ def moe_ffn(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
             raise ValueError("%s must be contiguous" % name)
     T, H = x.shape
     E, I, k = w1.shape[0], w2.shape[2], ids.shape[1]
-    if tuple(w1.shape) != (E, 2 * I, H) or tuple(w2.shape) != (E, H, I):
+    if w4:
+        # H is x's and I the scales': a byte count cannot tell I from I + 1
+        I = w2_scale_log2.shape[2] * reference.MXFP4_BLOCK
+        if (tuple(w1.shape) != (E, 2 * I, H // 2) or
+                tuple(w2.shape) != (E, H, I // 2)):
+            raise ValueError("MXFP4 w1 must be [E, 2I, H/2] and w2 [E, H, "
+                             "I/2], got %s and %s for H = %d, I = %d" % (
+                                 tuple(w1.shape), tuple(w2.shape), H, I))
+    elif tuple(w1.shape) != (E, 2 * I, H) or tuple(w2.shape) != (E, H, I):
         raise ValueError("w1 must be [E, 2I, H] and w2 [E, H, I], got %s and "
                          "%s for H = %d" % (tuple(w1.shape), tuple(w2.shape),
                                             H))
@@ -296,13 +322,16 @@ def moe_ffn(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
         raise ValueError("moe_ffn needs E <= %d, k <= min(%d, E), H %% 256 == "
                          "0 and I %% 64 == 0, got E = %d, k = %d, H = %d, I = "
                          "%d" % (MOE_MAX_EXPERTS, MOE_MAX_TOP_K, E, k, H, I))
-    if w8:
-        for e, name, rows in ((w1_scale_log2, "w1_scale_log2", 2 * I),
-                              (w2_scale_log2, "w2_scale_log2", H)):
-            if (e.dtype != torch.int8 or tuple(e.shape) != (E, rows) or
+    if w8 or w4:
+        for e, name, shape in (
+                (w1_scale_log2, "w1_scale_log2",
+                 (E, 2 * I, H // 32) if w4 else (E, 2 * I)),
+                (w2_scale_log2, "w2_scale_log2",
+                 (E, H, I // 32) if w4 else (E, H))):
+            if (e.dtype != torch.int8 or tuple(e.shape) != shape or
                     not e.is_contiguous() or e.device != x.device):
                 raise ValueError("%s must be contiguous int8 %s on %s, got "
-                                 "%s %s on %s" % (name, (E, rows), x.device,
+                                 "%s %s on %s" % (name, shape, x.device,
                                                   tuple(e.shape), e.dtype,
                                                   e.device))
     if T == 0:
@@ -323,8 +352,13 @@ def moe_ffn(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
             w1, w2 = (reference.dequantize_weight_e4m3(
                 t.view(-1, t.shape[2]), e.view(-1)).view(t.shape)
                 for t, e in ((w1, w1_scale_log2), (w2, w2_scale_log2)))
+        if w4:
+            w1, w2 = (reference.dequantize_weight_mxfp4(
+                t.view(-1, t.shape[2]), e.view(-1, e.shape[2])).view(
+                    t.shape[0], t.shape[1], -1)
+                for t, e in ((w1, w1_scale_log2), (w2, w2_scale_log2)))
         return reference.moe_ffn(x, w1, w2, ids, w)
-    if w8:
+    if w8 or w4:
         return _require_hip().moe_ffn(x, w1, w2, w, group[1], group[2],
                                       w1_scale_log2, w2_scale_log2)
     return _require_hip().moe_ffn(x, w1, w2, w, group[1], group[2])

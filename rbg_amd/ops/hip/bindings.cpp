@@ -781,15 +781,36 @@ void check_i32_on(const torch::Tensor& t, const char* name,
 // The expert weights of one layer, w1 [E, 2I, H] and w2 [E, H, I] on x's
 // device, for the shapes the grouped GEMMs serve: both bf16 and no exponents,
 // or both e4m3 with e1 int8 [E, 2I] and e2 int8 [E, H] (docs/FEATURES.md "FP8
-// experts").
-void check_moe_experts(const torch::Tensor& x, const torch::Tensor& w1,
-                       const torch::Tensor& w2,
-                       const c10::optional<torch::Tensor>& e1,
-                       const c10::optional<torch::Tensor>& e2) {
+// experts"), or both uint8 e2m1 codes, w1 [E, 2I, H/2] and w2 [E, H, I/2],
+// with e1 int8 [E, 2I, H/32] and e2 int8 [E, H, I/32] ("MXFP4 experts").
+// Returns I.
+int64_t check_moe_experts(const torch::Tensor& x, const torch::Tensor& w1,
+                          const torch::Tensor& w2,
+                          const c10::optional<torch::Tensor>& e1,
+                          const c10::optional<torch::Tensor>& e2) {
   check_bf16_contig(x, "x");
   TORCH_CHECK(w1.scalar_type() == w2.scalar_type(),
               "w1 and w2 must have one dtype");
-  if (w1.scalar_type() == torch::kFloat8_e4m3fn) {
+  const bool w4 = w1.scalar_type() == torch::kByte;
+  if (w4) {
+    TORCH_CHECK(e1.has_value() && e2.has_value(),
+                "MXFP4 experts need w1_scale_log2 and w2_scale_log2");
+    const torch::Tensor* w[2] = {&w1, &w2};
+    const torch::Tensor* e[2] = {&*e1, &*e2};
+    for (int i = 0; i < 2; ++i) {
+      TORCH_CHECK(w[i]->is_cuda() && w[i]->is_contiguous() &&
+                      (uintptr_t)w[i]->data_ptr() % 16 == 0,
+                  "an MXFP4 expert weight must be contiguous on GPU");
+      TORCH_CHECK(e[i]->scalar_type() == torch::kChar &&
+                      e[i]->is_contiguous() && e[i]->dim() == 3 &&
+                      w[i]->dim() == 3 && e[i]->size(0) == w[i]->size(0) &&
+                      e[i]->size(1) == w[i]->size(1) &&
+                      e[i]->size(2) * 16 == w[i]->size(2) &&
+                      e[i]->device() == x.device(),
+                  "an MXFP4 expert scale must be contiguous int8 [E, rows of "
+                  "its weight, K / 32] on x's device");
+    }
+  } else if (w1.scalar_type() == torch::kFloat8_e4m3fn) {
     TORCH_CHECK(e1.has_value() && e2.has_value(),
                 "e4m3 experts need w1_scale_log2 and w2_scale_log2");
     const torch::Tensor* w[2] = {&w1, &w2};
@@ -818,13 +839,18 @@ void check_moe_experts(const torch::Tensor& x, const torch::Tensor& w1,
               "w1 must be [E, 2I, H] and w2 [E, H, I]");
   TORCH_CHECK(w1.device() == x.device() && w2.device() == x.device(),
               "x/w1/w2 device mismatch");
-  const int64_t H = x.size(1), E = w1.size(0), I = w2.size(2);
+  // two codes per MXFP4 byte: I from the scales, as H is from x
+  const int64_t H = x.size(1), E = w1.size(0);
+  const int64_t I = w4 ? e2->size(2) * 32 : w2.size(2), per = w4 ? 2 : 1;
   TORCH_CHECK(E >= 1 && E <= kMoeMaxExperts, "E must be in [1, 256], got ", E);
   TORCH_CHECK(H >= 256 && H % 256 == 0, "H must be a multiple of 256, got ",
               H);
   TORCH_CHECK(I >= 64 && I % 64 == 0, "I must be a multiple of 64, got ", I);
-  TORCH_CHECK(w1.size(1) == 2 * I && w1.size(2) == H, "w1 must be [E, 2I, H]");
-  TORCH_CHECK(w2.size(0) == E && w2.size(1) == H, "w2 must be [E, H, I]");
+  TORCH_CHECK(w1.size(1) == 2 * I && w1.size(2) * per == H,
+              "w1 must be [E, 2I, H] (MXFP4: [E, 2I, H/2])");
+  TORCH_CHECK(w2.size(0) == E && w2.size(1) == H && w2.size(2) * per == I,
+              "w2 must be [E, H, I] (MXFP4: [E, H, I/2])");
+  return I;
 }
 
 }  // namespace
@@ -870,14 +896,15 @@ std::vector<torch::Tensor> moe_group(torch::Tensor ids, int64_t E) {
 }
 
 // y bf16 [T, H] from the grouping of moe_route / moe_group.  e4m3 w1 and w2
-// come with their int8 exponents and stand for dq = e4m3 * 2^e[expert, row].
+// come with their int8 exponents and stand for dq = e4m3 * 2^e[expert, row];
+// uint8 ones are MXFP4 codes and stand for e2m1 * 2^e[expert, row, k / 32].
 torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor w1, torch::Tensor w2,
                       torch::Tensor weights, torch::Tensor expert_offsets,
                       torch::Tensor sorted_pairs,
                       c10::optional<torch::Tensor> w1_scale_log2,
                       c10::optional<torch::Tensor> w2_scale_log2) {
-  check_moe_experts(x, w1, w2, w1_scale_log2, w2_scale_log2);
-  const int64_t T = x.size(0), H = x.size(1), E = w1.size(0), I = w2.size(2);
+  const int64_t I = check_moe_experts(x, w1, w2, w1_scale_log2, w2_scale_log2);
+  const int64_t T = x.size(0), H = x.size(1), E = w1.size(0);
   TORCH_CHECK(weights.is_cuda() && weights.device() == x.device() &&
                   weights.scalar_type() == torch::kFloat32 &&
                   weights.is_contiguous() && weights.dim() == 2 &&
@@ -911,6 +938,8 @@ torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor w1, torch::Tensor w2,
   if (w1_scale_log2.has_value()) {
     a.w1_exp = w1_scale_log2->data_ptr();
     a.w2_exp = w2_scale_log2->data_ptr();
+    a.format = w1.scalar_type() == torch::kByte ? MoeFfnLaunch::MXFP4
+                                                : MoeFfnLaunch::E4M3;
   }
   LAUNCH(launch_moe_ffn, a, current_stream());
   return y;

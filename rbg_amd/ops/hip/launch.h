@@ -108,10 +108,13 @@ struct KvPeerCopyLaunch {
 
 // The three launches behind the grouping of a mixture-of-experts FFN
 // (moe.hip): grouped gate_up + SwiGLU, grouped down, weighted combine.
-// 1 <= k <= 8, E <= 256, H % 256 == 0, I % 64 == 0.  w1_exp and w2_exp are
-// both null (bf16 w1, w2) or both set: w1 and w2 are then e4m3 bytes and the
-// exponents one int8 per expert output row, 4-byte aligned.
+// 1 <= k <= 8, E <= 256, H % 256 == 0, I % 64 == 0.  format tells what w1
+// and w2 hold.  BF16: w1_exp and w2_exp are null.  E4M3: bytes, and the
+// exponents one int8 per expert output row, 4-byte aligned.  MXFP4: e2m1
+// codes, two per byte (w1 [E, 2 * I, H / 2], w2 [E, H, I / 2], 16-byte
+// aligned), and the exponents one int8 per 32 k of a row.
 struct MoeFfnLaunch {
+  enum Format { BF16, E4M3, MXFP4 };
   void* y;                     // [T, H] bf16
   void* h;                     // [T * k, I] bf16 workspace, sorted order
   void* opart;                 // [T * k, H] f32 workspace, pair order
@@ -122,8 +125,9 @@ struct MoeFfnLaunch {
   const void* expert_offsets;  // [E + 1] int32
   const void* sorted_pairs;    // [T * k] int32: pairs t * k + j by expert
   int T, k, E, H, I;
-  const void* w1_exp = nullptr;  // [E, 2 * I] int8
-  const void* w2_exp = nullptr;  // [E, H] int8
+  const void* w1_exp = nullptr;  // [E, 2 * I] int8; MXFP4 [E, 2 * I, H / 32]
+  const void* w2_exp = nullptr;  // [E, H] int8; MXFP4 [E, H, I / 32]
+  Format format = BF16;
 };
 
 extern "C" {

@@ -77,6 +77,30 @@
 //           is the bf16 kernel's result on dq bit for bit: a power of two
 //           commutes with every rounding on the way.
 //
+// MXFP4 experts (docs/FEATURES.md "MXFP4 experts"): w1 / w2 as e2m1 codes,
+// two per byte (element 2i in the low nibble), with one int8 exponent per 32
+// consecutive k of a row, dq = e2m1 * 2^e.  The third instantiation
+// (WT = mxfp4_t) again differs in how W travels only:
+//   stage = 128 k as above, and A's staging is the e4m3 pass's.  W's 64 rows
+//           x 64 B of codes are ONE 16-byte piece per thread (row tid >> 2,
+//           piece tid & 3), which is exactly one 32-k scale block: the thread
+//           loads that block's exponent byte with it (the exponents of a row
+//           are K/32 bytes, 2-byte aligned at K = 192: byte loads only).
+//   LDS   = W stays CODES.  Row pitch 80 B = 64 B of codes, the stage's four
+//           exponent bytes of the row, pad.  80 B is 20 banks: the 16 rows
+//           of a tile start on 16 distinct multiples of 4 banks and the four
+//           4-byte reads of a row's k-groups fill the gaps, so the fragment
+//           reads are conflict-free and the 16-byte writes stay aligned.
+//           Two buffers are 45 056 B at MT = 4 (three workgroups per CU).
+//   frag  = a lane's 8 consecutive k are one 4-byte read and four
+//           v_cvt_scalef32_pk_bf16_fp4 (byte select 0 .. 3) whose scale
+//           operand is the f32 2^e of the lane's (row, block), one byte read:
+//           the bf16x8 of dq, exact.  The MFMA consumes 32 k per W row, one
+//           scale block, so nothing is left for the epilogue to scale.
+//   tail  = as above: blocks past K are re-reads of the row's last block
+//           with that block's exponent, and the second 64-k step is skipped.
+//   chain = unchanged, so the result is the bf16 kernel's on dq bit for bit.
+//
 // No atomics on floats anywhere; the one atomic is the integer ticket (and
 // integer LDS counters inside the sort, whose totals do not depend on order).
 // All global writes are plain vector stores.
@@ -87,6 +111,8 @@
 #pragma clang attribute push(                                               \
     __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
 #endif
+
+#include <type_traits>
 
 #include "skinny_gemm_tile.h"   // lds_frag
 #include "launch.h"
@@ -511,6 +537,140 @@ DEV_INLINE void mg_pass_w8(unsigned char* stage,
 #undef M8_LD
 }
 
+// MXFP4 W: 128-k stages, W as codes with their exponents in LDS (the file
+// header has the layout).  The tag type tells the instantiation from e4m3's.
+struct mxfp4_t { uint8_t codes; };
+constexpr int M4_WPITCH = 80;                // 64 B codes, 4 exponents, pad
+constexpr int M4_W_BYTES = 64 * M4_WPITCH;
+constexpr int M4_STAGE_BYTES =
+    2 * (M4_W_BYTES + 16 * MG_MT * M8_APITCH * 2);
+constexpr int M4_LDS_BYTES =
+    M4_STAGE_BYTES > MG_RED_BYTES ? M4_STAGE_BYTES : MG_RED_BYTES;
+
+// MFMA fragment from 8 staged e2m1 codes of one row: row points at the
+// staged row, cb is the byte of the lane's first code and blk its scale
+// block within the stage.  dq = e2m1 * 2^e comes out of the conversion.
+DEV_INLINE bf16x8 lds_frag_w4(const unsigned char* row, const int cb,
+                              const int blk) {
+  const unsigned codes = *reinterpret_cast<const unsigned*>(row + cb);
+  const float scale =
+      w8_exp2i(reinterpret_cast<const signed char*>(row)[64 + blk]);
+  union { bf16x2 v; unsigned u; } p0, p1, p2, p3;
+  p0.v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 0);
+  p1.v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 1);
+  p2.v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 2);
+  p3.v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 3);
+  union { uint4 u; bf16x8 v; } cvt;
+  cvt.u = make_uint4(p0.u, p1.u, p2.u, p3.u);
+  return cvt.v;
+}
+
+// mg_pass for MXFP4 W.  wrow / erow: the codes and the exponents of this
+// thread's W row (stage row tid >> 2) at k = 0; ab0..ab3 as in mg_pass_w8.
+// The thread's block within a stage is added here, clamped to the row's last.
+template <int MT>
+DEV_INLINE void mg_pass_w4(unsigned char* stage,
+                           const uint8_t* __restrict__ wrow,
+                           const int8_t* __restrict__ erow,
+                           const __hip_bfloat16* __restrict__ ab0,
+                           const __hip_bfloat16* __restrict__ ab1,
+                           const __hip_bfloat16* __restrict__ ab2,
+                           const __hip_bfloat16* __restrict__ ab3,
+                           const int nsteps, f32x4 (&acc)[MT][2]) {
+  constexpr int BUF = M4_W_BYTES + 16 * MT * M8_APITCH * 2;
+  constexpr bool A4 = MT > 1;                // four A pieces per thread
+  static_assert(MT == 1 || MT == 4, "one or four A pieces per thread");
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int gl = lane & 15, gslice = lane >> 4;
+  const int t0 = wave & 1, k_slice = wave >> 1;
+  const int wr = tid >> 2, wblk = tid & 3;            // W: row, block of stage
+  const int arow = tid >> 4, achk = (tid & 15) * 8;   // A: bf16
+  const int K = nsteps * MG_KSTEP;
+  const int nstages = (nsteps + 1) >> 1;
+  const int nblocks = K / 32;
+
+  uint4 w0, a00, a01 = {}, a02 = {}, a03 = {};
+  uint4 w1, a10, a11 = {}, a12 = {}, a13 = {};
+  int e0, e1;
+#define M4_LD(p, kb) (*reinterpret_cast<const uint4*>((p) + (kb)))
+#define M4_ISSUE(stg, wa, ea, aa, ab, ac, ad)                               \
+  do {                                                                      \
+    const int s = min(stg, nstages - 1);                                    \
+    const int ka = min(s * M8_KSTAGE + achk, K - 8);                        \
+    const int blk = min(s * 4 + wblk, nblocks - 1);                         \
+    aa = M4_LD(ab0, ka);                                                    \
+    if (A4) {                                                               \
+      ab = M4_LD(ab1, ka);                                                  \
+      ac = M4_LD(ab2, ka);                                                  \
+      ad = M4_LD(ab3, ka);                                                  \
+    }                                                                       \
+    wa = M4_LD(wrow, blk * 16);                                             \
+    ea = erow[blk];                                                         \
+  } while (0)
+#define M4_AST(st, row)                                                     \
+  reinterpret_cast<uint4*>((st) + M4_W_BYTES +                              \
+                           ((row) * M8_APITCH + achk) * 2)
+#define M4_WRITE(st, wa, ea, aa, ab, ac, ad)                                \
+  do {                                                                      \
+    *reinterpret_cast<uint4*>((st) + wr * M4_WPITCH + wblk * 16) = wa;      \
+    (st)[wr * M4_WPITCH + 64 + wblk] = (unsigned char)ea;                   \
+    *M4_AST(st, arow) = aa;                                                 \
+    if (A4) {                                                               \
+      *M4_AST(st, 16 + arow) = ab;                                          \
+      *M4_AST(st, 32 + arow) = ac;                                          \
+      *M4_AST(st, 48 + arow) = ad;                                          \
+    }                                                                       \
+  } while (0)
+
+  // stage `stg` of buffer st: its first 64-k step, and its second unless the
+  // step count is odd and this is the last stage
+  auto compute = [&](const unsigned char* st, const int stg) {
+    const __hip_bfloat16* ast =
+        reinterpret_cast<const __hip_bfloat16*>(st + M4_W_BYTES);
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      if (half == 1 && 2 * stg + 1 >= nsteps) break;
+      const int kf = half * MG_KSTEP + k_slice * 32 + gslice * 8;
+      const int blk = half * 2 + k_slice;
+      const bf16x8 wf0 =
+          lds_frag_w4(&st[(t0 * 16 + gl) * M4_WPITCH], kf >> 1, blk);
+      const bf16x8 wf1 =
+          lds_frag_w4(&st[((t0 + 2) * 16 + gl) * M4_WPITCH], kf >> 1, blk);
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) {
+        const bf16x8 af = lds_frag(&ast[(mt * 16 + gl) * M8_APITCH + kf]);
+        acc[mt][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            wf0, af, acc[mt][0], 0, 0, 0);
+        acc[mt][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            wf1, af, acc[mt][1], 0, 0, 0);
+      }
+    }
+  };
+
+  unsigned char* buf0 = stage;
+  unsigned char* buf1 = stage + BUF;
+  M4_ISSUE(0, w0, e0, a00, a01, a02, a03);
+  M4_ISSUE(1, w1, e1, a10, a11, a12, a13);
+  M4_WRITE(buf0, w0, e0, a00, a01, a02, a03);
+  M4_ISSUE(2, w0, e0, a00, a01, a02, a03);
+  for (int stg = 0; stg < nstages; stg += 2) {
+    __syncthreads();
+    compute(buf0, stg);
+    M4_WRITE(buf1, w1, e1, a10, a11, a12, a13);
+    M4_ISSUE(stg + 3, w1, e1, a10, a11, a12, a13);
+    if (stg + 1 >= nstages) break;           // odd stage count
+    __syncthreads();
+    compute(buf1, stg + 1);
+    M4_WRITE(buf0, w0, e0, a00, a01, a02, a03);
+    M4_ISSUE(stg + 4, w0, e0, a00, a01, a02, a03);
+  }
+#undef M4_WRITE
+#undef M4_AST
+#undef M4_ISSUE
+#undef M4_LD
+}
+
 struct MoeGemmArgs {
   void* out;                  // GATE_UP: h bf16 [TK, N]; else opart f32 [TK, N]
   const __hip_bfloat16* a;    // GATE_UP: x [T, K]; else h [TK, K]
@@ -518,17 +678,22 @@ struct MoeGemmArgs {
   const int* offsets;         // [E + 1]
   const int* sorted;          // [TK]
   int TK, k, K, N, panels;
-  const int8_t* wexp;         // e4m3 w: [E, 2N] or [E, N] exponents; else null
+  // e4m3 w: [E, 2N] or [E, N] exponents; MXFP4 w: [E, 2N, K / 32] or
+  // [E, N, K / 32]; else null
+  const int8_t* wexp;
 };
 
 // All passes of one expert's rows at MT row tiles per pass.
 // WT: __hip_bfloat16, or uint8_t for e4m3 W, whose exponents for this panel's
-// stage rows start at we (gate rows; the up rows' are g.N further).
+// stage rows start at we (gate rows; the up rows' are g.N further), or
+// mxfp4_t: wb0 and we are then the codes and the exponents of this thread's
+// one W row.
 template <int MT, bool GATE_UP, typename WT>
 DEV_INLINE void mg_expert(const MoeGemmArgs& g, unsigned char* smem,
                           const WT* wb0, const WT* wb1, const int8_t* we,
                           const int off, const int n, const int panel) {
-  constexpr bool W8 = sizeof(WT) == 1;
+  constexpr bool W8 = std::is_same<WT, uint8_t>::value;
+  constexpr bool W4 = std::is_same<WT, mxfp4_t>::value;
   __hip_bfloat16* stage = reinterpret_cast<__hip_bfloat16*>(smem);
   float* red = reinterpret_cast<float*>(smem);
   const int tid = threadIdx.x;
@@ -557,7 +722,7 @@ DEV_INLINE void mg_expert(const MoeGemmArgs& g, unsigned char* smem,
       acc[mt][0] = {0.f, 0.f, 0.f, 0.f};
       acc[mt][1] = {0.f, 0.f, 0.f, 0.f};
     }
-    if constexpr (W8) {
+    if constexpr (W8 || W4) {
       // tile rows arow + 16 i of this pass, 16 lanes per row
       const __hip_bfloat16* ab[4];
 #pragma unroll
@@ -568,7 +733,12 @@ DEV_INLINE void mg_expert(const MoeGemmArgs& g, unsigned char* smem,
                                   : (size_t)s;
         ab[i] = g.a + ar * g.K;
       }
-      mg_pass_w8<MT>(smem, wb0, wb1, ab[0], ab[1], ab[2], ab[3], nsteps, acc);
+      if constexpr (W4)
+        mg_pass_w4<MT>(smem, &wb0->codes, we, ab[0], ab[1], ab[2], ab[3],
+                       nsteps, acc);
+      else
+        mg_pass_w8<MT>(smem, wb0, wb1, ab[0], ab[1], ab[2], ab[3], nsteps,
+                       acc);
     } else {
       mg_pass<MT>(stage, wb0, wb1, g.a + ar0 * g.K + schk,
                   g.a + ar1 * g.K + schk, nsteps, acc);
@@ -641,9 +811,10 @@ DEV_INLINE void mg_expert(const MoeGemmArgs& g, unsigned char* smem,
 
 template <bool GATE_UP, typename WT>
 __global__ __launch_bounds__(MG_NT) void moe_gemm_kernel(const MoeGemmArgs g) {
-  constexpr bool W8 = sizeof(WT) == 1;
+  constexpr bool W8 = std::is_same<WT, uint8_t>::value;
+  constexpr bool W4 = std::is_same<WT, mxfp4_t>::value;
   __shared__ __attribute__((aligned(16))) unsigned char
-      smem[W8 ? M8_LDS_BYTES : MG_LDS_BYTES];
+      smem[W8 ? M8_LDS_BYTES : W4 ? M4_LDS_BYTES : MG_LDS_BYTES];
   const int e = blockIdx.x / g.panels;
   const int panel = blockIdx.x % g.panels;
   const int off = min(max(g.offsets[e], 0), g.TK);
@@ -655,7 +826,14 @@ __global__ __launch_bounds__(MG_NT) void moe_gemm_kernel(const MoeGemmArgs g) {
   const WT* wb0;
   const WT* wb1;
   const int8_t* we = nullptr;
-  if (GATE_UP) {              // stage rows [0, 32) gate, [32, 64) up
+  if constexpr (W4) {         // one W row per thread: stage row tid >> 2
+    const int r = threadIdx.x >> 2;
+    const size_t row =
+        GATE_UP ? (size_t)e * 2 * g.N + (r >> 5) * g.N + panel * 32 + (r & 31)
+                : (size_t)e * g.N + panel * 64 + r;
+    wb0 = wb1 = w + row * (g.K / 2);
+    we = g.wexp + row * (g.K / 32);
+  } else if (GATE_UP) {       // stage rows [0, 32) gate, [32, 64) up
     wb0 = w + ((size_t)e * 2 * g.N + panel * 32 + srow) * g.K + schk;
     wb1 = wb0 + (size_t)g.N * g.K;
     if (W8) we = g.wexp + (size_t)e * 2 * g.N + panel * 32;
@@ -735,8 +913,10 @@ hipError_t launch_moe_ffn(const MoeFfnLaunch& a, hipStream_t stream) {
   if (a.T < 1 || a.k < 1 || a.k > 8 || a.E < 1 || a.E > MR_EMAX ||
       a.H < 256 || a.H % 256 || a.I < 64 || a.I % 64)
     return hipErrorInvalidValue;
-  const bool w8 = a.w1_exp != nullptr;
-  if (w8 != (a.w2_exp != nullptr)) return hipErrorInvalidValue;
+  const bool scaled = a.w1_exp != nullptr;
+  if (scaled != (a.w2_exp != nullptr) ||
+      scaled != (a.format != MoeFfnLaunch::BF16))
+    return hipErrorInvalidValue;
   const int TK = a.T * a.k;
   const MoeGemmArgs gu = {a.h, (const __hip_bfloat16*)a.x, a.w1,
                           (const int*)a.expert_offsets,
@@ -747,7 +927,10 @@ hipError_t launch_moe_ffn(const MoeFfnLaunch& a, hipStream_t stream) {
                           (const int*)a.sorted_pairs, TK, a.k, a.I, a.H,
                           a.H / 64, (const int8_t*)a.w2_exp};
   const dim3 ggu(a.E * gu.panels), gdn(a.E * dn.panels), block(MG_NT);
-  if (w8) {
+  if (a.format == MoeFfnLaunch::MXFP4) {
+    moe_gemm_kernel<true, mxfp4_t><<<ggu, block, 0, stream>>>(gu);
+    moe_gemm_kernel<false, mxfp4_t><<<gdn, block, 0, stream>>>(dn);
+  } else if (a.format == MoeFfnLaunch::E4M3) {
     moe_gemm_kernel<true, uint8_t><<<ggu, block, 0, stream>>>(gu);
     moe_gemm_kernel<false, uint8_t><<<gdn, block, 0, stream>>>(dn);
   } else {

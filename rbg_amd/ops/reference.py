@@ -134,6 +134,69 @@ def dequantize_weight_e4m3(w8: torch.Tensor, e: torch.Tensor
                        e.to(torch.int32).view(-1, 1)).to(torch.bfloat16)
 
 
+# MXFP4 expert weights (docs/FEATURES.md "MXFP4 experts"): e2m1 codes, two per
+# byte (element 2i in the low nibble), with one power-of-two exponent per 32
+# consecutive k of a row, int8 [N, K / 32].  Code = s eem; the dense
+# projections have no MXFP4, so the experts' option has a tuple of its own.
+EXPERT_WEIGHT_DTYPES = WEIGHT_DTYPES + ("mxfp4",)
+MXFP4_BLOCK = 32
+E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+# (midpoint between codes c and c + 1, whether the tie goes up to c + 1: it
+# does where c + 1 has mantissa bit 0, that is where c is odd)
+_E2M1_MIDPOINTS = tuple(((E2M1_GRID[c] + E2M1_GRID[c + 1]) / 2, c % 2 == 1)
+                        for c in range(7))
+
+
+def quantize_weight_mxfp4(w: torch.Tensor
+                          ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """W bf16 [N, K] -> (codes uint8 [N, K / 2], e int8 [N, K / 32]).  Per
+    block of 32 k, e is the smallest integer with amax <= 6 * 2^e (clamped to
+    W_SCALE_LOG2_RANGE, 0 for a zero block): amax = m * 2^x with m in
+    [0.5, 1) and 6 = 0.75 * 2^3, so e = x - 3 where m <= 0.75 and x - 2
+    above; no division.  W * 2^-e (exact) is rounded to the nearest e2m1
+    value, ties to the code with mantissa bit 0, saturating at +-6."""
+    if w.dim() != 2 or w.shape[1] % MXFP4_BLOCK:
+        raise ValueError("an MXFP4 weight is [N, K] with K %% %d == 0, got %s"
+                         % (MXFP4_BLOCK, tuple(w.shape)))
+    wf = w.float()
+    if not bool(torch.isfinite(wf).all()):
+        raise ValueError("a non-finite weight has no e2m1 code")
+    N, K = wf.shape
+    blocks = wf.view(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = blocks.abs().amax(dim=2)
+    m, x = torch.frexp(amax)
+    e = torch.where(m <= 0.75, x - 3, x - 2)
+    e = torch.where(amax > 0, e, torch.zeros_like(e))
+    e = e.clamp(*W_SCALE_LOG2_RANGE)
+    mag = torch.ldexp(blocks.abs(), -e.to(torch.int32).unsqueeze(2))
+    code = torch.zeros_like(mag, dtype=torch.uint8)
+    for mid, tie_up in _E2M1_MIDPOINTS:
+        code += (mag >= mid if tie_up else mag > mid).to(torch.uint8)
+    code |= torch.signbit(blocks).to(torch.uint8) << 3
+    code = code.view(N, K // 2, 2)
+    return code[..., 0] | (code[..., 1] << 4), e.to(torch.int8)
+
+
+def dequantize_weight_mxfp4(codes: torch.Tensor, e: torch.Tensor
+                            ) -> torch.Tensor:
+    """dq[n, k] = e2m1(code[n, k]) * 2^e[n, k / 32] as bf16: exact, and a
+    normal bf16 or zero for every |e| <= 64."""
+    if codes.dtype != torch.uint8 or e.dtype != torch.int8 or \
+            codes.dim() != 2 or e.dim() != 2 or \
+            codes.shape[1] % (MXFP4_BLOCK // 2) or \
+            tuple(e.shape) != (codes.shape[0],
+                               codes.shape[1] // (MXFP4_BLOCK // 2)):
+        raise ValueError("need uint8 [N, K / 2] and int8 [N, K / 32], got %s "
+                         "%s and %s %s" % (codes.dtype, tuple(codes.shape),
+                                           e.dtype, tuple(e.shape)))
+    N = codes.shape[0]
+    nib = torch.stack((codes & 15, codes >> 4), dim=2).view(N, -1).long()
+    grid = torch.tensor(E2M1_GRID + tuple(-v for v in E2M1_GRID),
+                        device=codes.device)
+    exp = e.to(torch.int32).repeat_interleave(MXFP4_BLOCK, dim=1)
+    return torch.ldexp(grid[nib], exp).to(torch.bfloat16)
+
+
 def kv_gather_dequant(cache: torch.Tensor, slots: torch.Tensor,
                       scale_log2: int = 0) -> torch.Tensor:
     page_size = cache.shape[2]

@@ -143,10 +143,11 @@ def engine_rows(args):
     model = "llama-3-8b"
     if args.engine_weights:       # FP8 projection weights over a bf16 pool
         variants = {"bf16": {}, "fp8w": dict(weight_dtype="fp8_e4m3")}
-    if args.engine_experts:       # FP8 expert weights of the MoE model
+    if args.engine_experts:       # quantised expert weights of the MoE model
         model = "qwen3-30b-a3b"
         variants = {"bf16": {},
-                    "fp8_experts": dict(expert_weight_dtype="fp8_e4m3")}
+                    "fp8_experts": dict(expert_weight_dtype="fp8_e4m3"),
+                    "mxfp4_experts": dict(expert_weight_dtype="mxfp4")}
     for name, kw in variants.items():
         cfg = EngineConfig(model=ModelConfig.preset(model),
                            device="cuda", max_batch_size=B,
@@ -209,7 +210,7 @@ def main() -> None:
                     help="engine rows only: bf16 against fp8_e4m3 weights")
     ap.add_argument("--engine-experts", action="store_true",
                     help="engine rows only: qwen3-30b-a3b, bf16 against "
-                         "fp8_e4m3 expert weights")
+                         "fp8_e4m3 and mxfp4 expert weights")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"

@@ -47,12 +47,14 @@ def time_calls(fn, n_layers, rounds, warmup=2):
     return times
 
 
-def w8_main(args, dev, shape):
+def quantised_main(args, dev, shape):
     """--w8: ops.moe_ffn with bf16 against e4m3 experts (the quantisation of
     the same weights), the two alternating call by call over the cold layer
-    sets.  TB/s counts each dtype's own weight bytes of the experts touched
+    sets; --w4: MXFP4 experts as a third format in the same alternation.
+    TB/s counts each format's own weight bytes of the experts touched
     (exponents included)."""
     E, K, H, I = shape
+    names = ("bf16", "e4m3", "mxfp4") if args.w4 else ("bf16", "e4m3")
     g = torch.Generator(device=dev).manual_seed(0)
     rnd = lambda *s: torch.randn(*s, device=dev, generator=g)
     sets = []
@@ -63,7 +65,15 @@ def w8_main(args, dev, shape):
         sets.append({"bf16": (w1, w2, None, None),
                      "e4m3": (q[0][0].view(w1.shape), q[1][0].view(w2.shape),
                               q[0][1].view(E, 2 * I), q[1][1].view(E, H))})
-    per_expert = {"bf16": 3 * I * H * 2, "e4m3": 3 * I * H + 2 * I + H}
+        if args.w4:
+            q = [ops.quantize_weight_mxfp4(w.view(-1, w.shape[2]))
+                 for w in (w1, w2)]
+            sets[-1]["mxfp4"] = (q[0][0].view(E, 2 * I, -1),
+                                 q[1][0].view(E, H, -1),
+                                 q[0][1].view(E, 2 * I, -1),
+                                 q[1][1].view(E, H, -1))
+    per_expert = {"bf16": 3 * I * H * 2, "e4m3": 3 * I * H + 2 * I + H,
+                  "mxfp4": 3 * I * H // 2 + 3 * I * H // 32}
     out = {"shape": {"E": E, "k": K, "H": H, "I": I}, "layers": args.layers}
     for T in (int(t) for t in args.tokens.split(",")):
         x = (rnd(T, H) * 0.5).bfloat16()
@@ -77,7 +87,7 @@ def w8_main(args, dev, shape):
                 return ops.moe_ffn(x, w1, w2, *routed[i])
             return ops.moe_ffn(x, w1, w2, *routed[i], e1, e2)
 
-        times = {"bf16": [], "e4m3": []}
+        times = {name: [] for name in names}
         for r in range(2 + args.rounds):
             for i in range(args.layers):
                 for name in times:
@@ -90,14 +100,18 @@ def w8_main(args, dev, shape):
                     if r >= 2:
                         times[name].append(s.elapsed_time(e) * 1e3)
         row = {"experts_touched": touched[0],
-               "cold": sum(touched) * per_expert["e4m3"] >= 2 * L3_BYTES}
+               "cold": sum(touched) * per_expert[names[-1]] >= 2 * L3_BYTES}
         for name, ts in times.items():
             med = statistics.median(ts)
             row[name + "_us"] = round(med, 1)
             row[name + "_us_min_max"] = [round(min(ts), 1), round(max(ts), 1)]
             row[name + "_weight_TBps"] = round(
                 sum(touched) / len(touched) * per_expert[name] / med / 1e6, 2)
-        row["e4m3_over_bf16"] = round(row["e4m3_us"] / row["bf16_us"], 3)
+        for name in names[1:]:
+            row[name + "_over_bf16"] = round(row[name + "_us"] /
+                                             row["bf16_us"], 3)
+        if args.w4:
+            row["mxfp4_over_e4m3"] = round(row["mxfp4_us"] / row["e4m3_us"], 3)
         out["T%d" % T] = row
     return out
 
@@ -111,11 +125,13 @@ def main():
     ap.add_argument("--w8", action="store_true",
                     help="bf16 against e4m3 experts instead of hip against "
                          "the loop")
+    ap.add_argument("--w4", action="store_true",
+                    help="bf16, e4m3 and MXFP4 experts, alternating")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     E, K, H, I = 128, 8, 2048, 768
-    if args.w8:
-        text = json.dumps(w8_main(args, dev, (E, K, H, I)), indent=1)
+    if args.w8 or args.w4:
+        text = json.dumps(quantised_main(args, dev, (E, K, H, I)), indent=1)
         print(text, flush=True)
         if args.out:
             with open(args.out, "w") as f:
